@@ -9,6 +9,11 @@ Workload = BASELINE.json configs[1]: 65 536 agents per GPU, visual=False, bodyra
 dt=0.0025 / ctrl_dt=0.02, ctrl_delay on, 3-slot comm-delay ring.  Agents shard trivially:
 each rank owns its own 65 536 agents (weak scaling), no data-path collective.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps once and prints the headline line (ms_per_step = that region / K).
+--full adds everything else: the repeated regions (median), the first region before spin-up, event / per-call / fused /
+sustained figures, kernel times and rooflines, the reset-heavy leg, the CPU baselines and the secondary legs.
+--dump-outputs DIR writes obs / reward / done of the last timed step as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -141,6 +146,27 @@ def cpu_baseline(consts, seconds_target=5.0, threads=None):
     out = cpu_baseline_env(consts, "hover", AGENTS_PER_GPU, seconds_target, threads)
     out["reference_recorded"] = REFERENCE_RECORDED
     return out
+
+
+DUMP_LIMIT_BYTES = 60_000_000      # --dump-outputs: 64 MB in all at most, with room for the .npy headers
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array (one row per agent) as <path>/<name>.npy in float32.  Above `limit` bytes in all, the same fixed,
+    seeded sample of rows from every array, sorted, with the sampled row numbers as agent_index.npy (float64)"""
+    arrays = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32) for k, v in arrays.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    assert len(rows) == 1, {k: a.shape for k, a in arrays.items()}
+    rows = rows.pop()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = int(limit // (total / rows + 8))              # + 8 B per row: its index
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["agent_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
 
 
 def bench_ppo(args, rank, world, dev, iters=None, cpu_ref=False):
@@ -490,7 +516,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=16, help="steps per vf_env_step_n call = depth of the (K,N,...) output ring (16 x 3.6 MB stays in the Infinity Cache; profiles/r02_reset_regime.txt)")
     ap.add_argument("--no-reset-leg", action="store_true", help="skip the U(-1,1) reset-heavy leg (kernel-trace profiles of the headline regime)")
     ap.add_argument("--spinup-ms", type=float, default=25.0, help="untimed device spin-up before the warm-up steps (clock governor); 0 = off")
-    ap.add_argument("--repeats", type=int, default=7, help="the timed --steps region is repeated; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed --steps region is repeated; the median is reported (default: 7 with "
+                                                               "--full, else 1: a plain run times exactly --steps steps)")
     ap.add_argument("--sustain-s", type=float, default=6.0, help="seconds of back-to-back stepping reported as `sustained` (the driver's "
                     "gpu_busy samples see the GPU working; 0 = off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -504,7 +531,18 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank joins the process group, one barrier, rank 0 prints the world size "
                          "(no GPU work; tests/test_parallel_gloo.py runs the plain `--gpus 2` command through it on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the first region before spin-up, event / per-call / fused / sustained figures, "
+                         "kernel times and rooflines, the reset-heavy leg, the CPU baselines and the secondary legs.  Without it the run "
+                         "sets up, warms up, times --steps steps once and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done of every agent) as DIR/<name>.npy in float32; "
+                         "the inputs depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "env" or args.launch_check):
+        ap.error("--dump-outputs: the headline workload (--workload env) only")
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))
 
@@ -579,43 +617,55 @@ def main():
             torch.cuda.synchronize()
 
     def run_steps(n, s):
-        """exactly n env steps, launch loop in C (vf_env_step_n): same kernels, same order, same outputs as n step() calls"""
+        """exactly n env steps, launch loop in C (vf_env_step_n): same kernels, same order, same outputs as n step() calls.
+        Returns what the last step_n call returned: (obs, reward, done), its last row = the n-th step's outputs"""
         done = 0
         while done < n:
             k = min(n - done, s.shape[0])
-            env.step_n(s if k == s.shape[0] else s[:k])
+            res = env.step_n(s if k == s.shape[0] else s[:k])
             done += k
+        return res
 
     # Device spin-up, disclosed as timing.spinup_steps: the driver's W = 5 warm-up steps last 60 us, the GPU's clock governor needs
     # ~20 ms of load to leave its idle state (a 20-step region right after process start runs at 12.85 us per step, the same region
     # after 2 000 untimed steps at 12.1 -- `--spinup-ms 0` switches this off).  Untimed, before the W warm-up steps; the timed
     # regions below still consist of exactly K steps each.
     # The contract read literally -- W untimed warm-up steps, then exactly K timed steps, nothing else before them -- measured once,
-    # right after process start and BEFORE the spin-up: reported as value_without_spinup next to the headline
-    run_steps(min(K, seq.shape[0]), seq)                  # first use of the K-step output buffers is an allocation (untimed)
-    if W > 0:
-        run_steps(W, wseq)
-    barrier()
-    t0 = time.perf_counter()
-    run_steps(K, seq)
-    torch.cuda.synchronize()
-    cold_el = time.perf_counter() - t0
-    barrier()
-    if dist is not None:
-        t = torch.tensor([cold_el], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        cold_el = float(t.item())
+    # right after process start and BEFORE the spin-up: reported as value_without_spinup next to the headline (--full only)
+    for k in sorted({seq.shape[0], K % seq.shape[0]} - {0}):
+        run_steps(k, seq)                                 # first use of the output buffers of each chunk length is an allocation (untimed)
+    cold_el = None
+    if args.full:
+        if W > 0:
+            run_steps(W, wseq)
+        barrier()
+        t0 = time.perf_counter()
+        run_steps(K, seq)
+        torch.cuda.synchronize()
+        cold_el = time.perf_counter() - t0
+        barrier()
+        if dist is not None:
+            t = torch.tensor([cold_el], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            cold_el = float(t.item())
     spin = int(args.spinup_ms * 1e3 / 11.0)
     if spin > 0:
         run_steps(spin, seq)
         torch.cuda.synchronize()
+    # a plain run times ONE region, and the first pass through the region's own path is slower (+0.16 us per step at --steps 20,
+    # median of 6 runs; --full's earlier regions absorb it): rehearse the region untimed first, at most 2 000 steps
+    rehearsal = 0 if args.full else min(K, 2000)
+    if rehearsal:
+        barrier()
+        run_steps(rehearsal, seq)
+        barrier()
     if W > 0:
         run_steps(W, wseq)
     walls, hosts, events, done_at = [], [], [], []
     for _ in range(max(1, args.repeats)):          # wall clock: nothing but the K launches between the two barriers
         barrier()
         t0 = time.perf_counter()
-        run_steps(K, seq)
+        last = run_steps(K, seq)
         t1 = time.perf_counter()
         tail.record()                              # drain(), with a time stamp in the middle:
         while not tail.query():
@@ -631,6 +681,45 @@ def main():
             el = float(t.item())
         walls.append(el)
         hosts.append(t1 - t0)
+    el = statistics.median(walls)
+    head = None
+    if rank == 0:
+        if args.dump_outputs:        # copied before anything else steps the env: step_n re-uses its output buffers
+            dump_outputs(args.dump_outputs, {name: t[-1] for name, t in zip(("obs", "reward", "done"), last)})
+        head = {
+            "metric": "agent-steps/sec (dynamics.step, visual=False)",
+            "value": world * N * K / el, "unit": "agent-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": el / K * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"HoverEnv.step (fused dynamics + collision + reward + done + on-device auto-reset), "
+                                   f"{N} agents/GPU, visual=False, bodyrate+euler, dt=0.0025/ctrl_dt=0.02, ctrl_delay, "
+                                   "3-slot delay ring, max_episode_steps=256 (BASELINE configs[1])",
+                       "agents_per_gpu": N, "parallelism": f"agents sharded x{world}, no data-path collective",
+                       "driver": "env.step_n(): the K launches of the timed region are enqueued by one C call "
+                                 "(vf_env_step_n); bit-identical to K env.step() calls (tests/test_env_multistep_gpu.py)"},
+            "timing": {"repeats": len(walls), "statistic": "median of the repeated --steps regions, each bracketed by barrier + synchronize; "
+                                                            "a rank's clock stops when ITS K steps have drained, the closing "
+                                                            "barrier follows, max over ranks",
+                       "ms_per_step_all": [w / K * 1e3 for w in walls], "ms_per_step_min": min(walls) / K * 1e3,
+                       "host_us_per_step": statistics.median(hosts) / K * 1e6,
+                       "ms_per_step_at_completion": statistics.median(done_at) / K * 1e3,
+                       "completion_note": "the same regions with the clock read when the event recorded behind the K launches reports "
+                                          "completion, i.e. without the ~20 us torch.cuda.synchronize() takes to return on an already "
+                                          "idle device (1 us per step at --steps 20); rank 0's figure",
+                       "spinup_steps": spin, "spinup_note": "untimed env steps before the W warm-up steps so that the device is at "
+                                                            "its sustained clocks (--spinup-ms, default 25 ms); value_without_spinup "
+                                                            "= the first K-step region of the process, timed right after W warm-up "
+                                                            "steps and before any spin-up (one region, max over ranks; --full only)",
+                       "rehearsal_steps": rehearsal},
+            "build": build_info,
+        }
+    if not args.full:
+        if head is not None:
+            print(json.dumps(head), flush=True)
+        env.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(3):                              # the same region on the device's clock (HIP events on the launch stream)
         barrier()
@@ -639,7 +728,6 @@ def main():
         e1.record()
         barrier()
         events.append(e0.elapsed_time(e1) * 1e-3)
-    el = statistics.median(walls)
     # how often the reset path ran in the last chunk: the share of agent-steps that ended an episode and the share of steps in
     # which at least one agent did (one wave per SIMD: the launch lasts as long as its slowest wave, so ANY reset costs the step)
     dn = env._rollouts[seq.shape[0]]["done"]
@@ -733,7 +821,6 @@ def main():
 
     out = None
     if rank == 0:
-        value = world * N * K / el
         achieved = BYTES_PER_ENV_STEP * N / (kern_us * 1e-6) / 1e9
         # HBM bytes per launch: NOT measured in this run -- read from the PMC pass committed under profiles/ (rocprofv3 --pmc in its
         # own run, as MI355X_MICROARCH.md prescribes; per-agent figure x N), and labelled as such (roofline.traffic_source)
@@ -762,36 +849,12 @@ def main():
                               "kernel time from this run"}
         except Exception:
             pass
-        out = {
-            "metric": "agent-steps/sec (dynamics.step, visual=False)",
-            "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": el / K * 1e3, "higher_is_better": True, "scaling": "weak",
-            "value_without_spinup": world * N * K / cold_el,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"HoverEnv.step (fused dynamics + collision + reward + done + on-device auto-reset), "
-                                   f"{N} agents/GPU, visual=False, bodyrate+euler, dt=0.0025/ctrl_dt=0.02, ctrl_delay, "
-                                   "3-slot delay ring, max_episode_steps=256 (BASELINE configs[1])",
-                       "agents_per_gpu": N, "parallelism": f"agents sharded x{world}, no data-path collective",
-                       "driver": "env.step_n(): the K launches of the timed region are enqueued by one C call "
-                                 "(vf_env_step_n); bit-identical to K env.step() calls (tests/test_env_multistep_gpu.py)"},
-            "timing": {"repeats": len(walls), "statistic": "median of the repeated --steps regions, each bracketed by barrier + synchronize; "
-                                                            "a rank's clock stops when ITS K steps have drained, the closing "
-                                                            "barrier follows, max over ranks",
-                       "ms_per_step_all": [w / K * 1e3 for w in walls], "ms_per_step_min": min(walls) / K * 1e3,
-                       "host_us_per_step": statistics.median(hosts) / K * 1e6,
-                       "event_us_per_step": statistics.median(events) / K * 1e6,
-                       "wall_over_kernel": el / K * 1e6 / kern_us, "per_call": per_call,
-                       "episode_end_rate": end_rate, "steps_with_a_reset": steps_with_reset,
-                       "ms_per_step_at_completion": statistics.median(done_at) / K * 1e3,
-                       "completion_note": "the same regions with the clock read when the event recorded behind the K launches reports "
-                                          "completion, i.e. without the ~20 us torch.cuda.synchronize() takes to return on an already "
-                                          "idle device (1 us per step at --steps 20); rank 0's figure",
-                       "spinup_steps": spin, "spinup_note": "untimed env steps before the W warm-up steps so that the device is at "
-                                                            "its sustained clocks (--spinup-ms, default 25 ms); value_without_spinup "
-                                                            "= the first K-step region of the process, timed right after W warm-up "
-                                                            "steps and before any spin-up (one region, max over ranks)",
-                       "ms_per_step_without_spinup": cold_el / K * 1e3},
-            "build": build_info,
+        out = dict(head, value_without_spinup=world * N * K / cold_el)
+        out["timing"] = dict(head["timing"], event_us_per_step=statistics.median(events) / K * 1e6,
+                             wall_over_kernel=el / K * 1e6 / kern_us, per_call=per_call,
+                             episode_end_rate=end_rate, steps_with_a_reset=steps_with_reset,
+                             ms_per_step_without_spinup=cold_el / K * 1e3)
+        out.update({
             "sustained": sustained,
             "with_resets": with_resets,
             "rollout_fused": {"value": world * N * K / fused_el, "unit": "agent-steps/s", "us_per_step": fused_el / K * 1e6,
@@ -810,7 +873,7 @@ def main():
                          "dyn_only": {"kernel": "k_dyn_step<bodyrate,euler,ctrl_delay>", "kernel_us": dyn_us,
                                       "bytes_per_agent_step": BYTES_PER_AGENT_STEP,
                                       "achieved": BYTES_PER_AGENT_STEP * N / (dyn_us * 1e-6) / 1e9}},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dyn.constants)
             out["cpu_baseline_1core"] = cpu_baseline(dyn.constants, seconds_target=3.0, threads=1)

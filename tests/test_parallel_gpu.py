@@ -158,7 +158,7 @@ def test_bench_two_ranks_control_flow(launcher):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(29900 + os.getpid() % 90)] + tail + ["--no-secondary"]
     else:
-        cmd = [sys.executable] + tail
+        cmd = [sys.executable] + tail + ["--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
