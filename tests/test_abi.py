@@ -17,7 +17,9 @@ def declared_symbols():
     return sorted(set(names))
 
 
-def test_header_symbols_exported():
+def test_header_symbols_exported_and_abi_version_mirrored():
+    """every declared symbol is exported and has a ctypes signature; library, binding and this test agree on VF_ABI_VERSION (11: the
+    fused optimiser-tail entry point of 10 was removed)"""
     import __graft_entry__ as ge
     ge.build()
     from visfly_amd import _lib
@@ -27,7 +29,7 @@ def test_header_symbols_exported():
     for s in syms:
         assert hasattr(L, s), f"{s} declared in include/ but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature in visfly_amd/_lib.py"
-    assert L.vf_abi_version() == _lib.ABI_VERSION == 10
+    assert L.vf_abi_version() == _lib.ABI_VERSION == 11
 
 
 def test_cfg_struct_size_matches_header():

@@ -1,6 +1,8 @@
 """k_mlp_forward_chain (32 rows per wave) vs k_mlp_forward_chain16 (16 rows per wave) in isolation: the BPTT actor (Hover / Racing
 state 13 -> [128, 64] -> pi [64, 64] -> 4, action head fused) at M rows, HIP events over 200 launches.
-    VISFLY_AMD_MLP_CHAIN16=0|1 python tools/exp_chain16.py [M]"""
+    python tools/exp_chain16.py [M]
+The library picks the kernel itself (16 rows per wave up to M = 16 384); the switch that forced the choice is gone, so an A/B of the
+two kernels at one M needs a build of each (profiles/r02_chain16_trace.txt has the r02 numbers)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch as th
@@ -22,4 +24,4 @@ for save in (True,):
             pol.forward_act(obs, eps, act, slot=0)
         e1.record(); th.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1) * 1e3 / 200)
-    print(f"M={M} chain16={os.environ.get('VISFLY_AMD_MLP_CHAIN16', 'auto')}: forward_act {best:.2f} us per launch (incl. host pacing)")
+    print(f"M={M} chain16={'yes' if M <= 16384 else 'no'}: forward_act {best:.2f} us per launch (incl. host pacing)")

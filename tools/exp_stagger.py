@@ -34,7 +34,7 @@ K = 400
 if mode == "single":
     env = make(N)
     A = actions(N, 16).repeat((K // 16, 1, 1)).contiguous()
-    print(f"stagger={os.environ.get('VISFLY_AMD_STAGGER', '0')} split={os.environ.get('VISFLY_AMD_SPLIT', 'auto')}: "
+    print(f"stagger={os.environ.get('VISFLY_AMD_STAGGER', '0')}: "
           f"kernel {env.time_steps(A[0], 400):.2f} us; ", end="")
     ws = []
     for _ in range(5):
@@ -66,5 +66,5 @@ else:
             run()
             torch.cuda.synchronize()
             ws.append((time.perf_counter() - t0) * 1e6 / K)
-        print(f"2 streams x {n} agents, stream 1 offset {off_us} us (split={os.environ.get('VISFLY_AMD_SPLIT', 'auto')}): "
+        print(f"2 streams x {n} agents, stream 1 offset {off_us} us: "
               f"{statistics.median(ws):.2f} us per full step")

@@ -73,7 +73,7 @@ env.step_n(AL)
 torch.cuda.synchronize()
 print(f"  step_n K={K_long}: {(time.perf_counter() - t0) * 1e6 / K_long:.2f} us/step")
 
-# ---- two streams, two half-size envs (plain kernel forced by VISFLY_AMD_SPLIT=0 in the environment if wanted)
+# ---- two streams, two half-size envs (kernel shape per launch as vf_common.hpp use_split picks it)
 for parts in (2, 4):
     n = N // parts
     envs = [make(n) for _ in range(parts)]

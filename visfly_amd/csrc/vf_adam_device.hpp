@@ -1,6 +1,5 @@
-// clip_grad_norm_ + torch.optim.Adam (weight decay as L2) on one parameter: the arithmetic shared by k_adam (vf_ppo.hip) and the
-// fused tail of the weight-gradient launch (vf_mlp_wgrad.hip) -- the same IEEE operations in the same order, so the two paths
-// agree to the bit.  Reference: utils/algorithms/PPO.py:285-292 (clip_grad_norm_, optimizer.step()).
+// clip_grad_norm_ + torch.optim.Adam (weight decay as L2) on one parameter: the arithmetic of k_adam (vf_ppo.hip).
+// Reference: utils/algorithms/PPO.py:285-292 (clip_grad_norm_, optimizer.step()).
 #pragma once
 #include <cmath>
 

@@ -46,16 +46,11 @@ inline int blocks_for(int n) { return (n + kBlock - 1) / kBlock; }
 
 // Kernel shape per launch: while one-thread-per-agent work cannot even give every SIMD a wave
 // (<= 32768 agents) the two-wave split (rotation | translation on co-resident waves) wins; from one
-// wave per SIMD on, the plain kernel issues fewer instructions in total and has no hand-off barriers.  VISFLY_AMD_SPLIT=0/1 forces a shape (A/B experiments).
+// wave per SIMD on, the plain kernel issues fewer instructions in total and has no hand-off barriers.
 inline bool use_split(int agents_padded, const vf_dyn_cfg& cfg)
 {
     // the geometric controller (velocity / position) needs the whole state in one thread
     if (cfg.action_type != VF_ACT_THRUST && cfg.action_type != VF_ACT_BODYRATE) return false;
-    static const int forced = [] {
-        const char* e = getenv("VISFLY_AMD_SPLIT");
-        return e ? atoi(e) : -1;
-    }();
-    if (forced >= 0) return forced != 0;
     return agents_padded <= 32768;   // measured on MI355X: 32768 agents 9.4 us (split) vs 11.3 us; 65536: 13.3 vs 12.5
 }
 
@@ -223,8 +218,5 @@ int mlp_wgrad_fold_blocks(const vf_mlp_bwd_desc* d);
 int mlp_wgrad_launch(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, double* sq_part,
                      const vf_stats_fold* loss_stats, hipStream_t st);
 int mlp_wgrad_launch_layers(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, unsigned layer_mask, hipStream_t st);
-// the same with fold, gradient norm, clip and Adam inside the weight-gradient launch: 1 launched, 0 not for this table / device, < 0 error
-int mlp_wgrad_adam_launch(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, const vf_stats_fold* loss_stats,
-                          const vf_wgrad_tail* tail, hipStream_t st);
 
 }  // namespace vf

@@ -18,16 +18,6 @@
 
 #pragma clang fp contract(off)
 
-#ifndef VF_SUBSTEP_UNROLL
-#define VF_SUBSTEP_UNROLL 1
-#endif
-// 1: IEEE-exact fast paths for sqrt and for the division by the (launch-uniform) mass, each behind a wave-uniform range
-// guard; every other value of the guard takes the compiler's own expansion.  A/B knob of tools/env_step_probe.hip, which
-// also checks both fast paths exhaustively against `sqrtf` / `x / m`.
-#ifndef VF_FAST_EXACT
-#define VF_FAST_EXACT 0
-#endif
-
 namespace vf {
 
 struct Quat {
@@ -59,41 +49,6 @@ __device__ __forceinline__ Quat qmul(const Quat& a, const Quat& b)
 }
 
 __device__ __forceinline__ Quat qconj(const Quat& a) { return Quat{a.w, -a.x, -a.y, -a.z}; }
-
-// ---- exact fp32 sqrt / division by a launch-uniform constant without the compiler's range handling ----------------
-// hipcc expands sqrtf (denormals preserved) to: rescale tiny inputs by 2^32, v_sqrt_f32 (<= 1 ulp), pick among the
-// result and its two neighbours by the sign of the fma residuals, undo the rescale, patch 0 / inf -- 16 instructions, 88
-// cycles for a lone wave (tools/valu_cost_probe).  For x = 0 or x >= 2^-96 (finite or not) the rescale and the patch are
-// no-ops: sqrt_exact_core is the remaining 9 instructions and returns the same bits.
-__device__ __forceinline__ float sqrt_exact_core(float x)
-{
-    float s = __builtin_amdgcn_sqrtf(x);
-    const float sd = __int_as_float(__float_as_int(s) - 1), su = __int_as_float(__float_as_int(s) + 1);
-    const float rd = __builtin_fmaf(-sd, s, x), ru = __builtin_fmaf(-su, s, x);
-    s = rd <= 0.0f ? sd : s;
-    s = ru > 0.0f ? su : s;
-    return s;
-}
-__device__ __forceinline__ float vf_sqrt(float x)
-{
-#if VF_FAST_EXACT == 2
-    return sqrt_exact_core(x);                          // measurement only: no guard
-#elif VF_FAST_EXACT
-    if (__builtin_amdgcn_ballot_w64(x < 0x1p-96f && x != 0.0f) == 0) return sqrt_exact_core(x);   // wave-uniform
-#endif
-    return sqrtf(x);
-}
-// x / m for a constant m with y = 1 / m (IEEE): twice-corrected reciprocal product.  Equal to the IEEE quotient for every
-// x with |x| in [2^-100, 2^100] (the residuals are exact there; tools/div_const_probe.hip, tools/env_step_probe.hip check all
-// 2^32 numerators); for x = 0 it returns +0 / -0 with possibly the other sign.
-__device__ __forceinline__ float div_const_core(float x, float m, float y)
-{
-    float q = x * y;
-    float e = __builtin_fmaf(-m, q, x);
-    q = __builtin_fmaf(e, y, q);
-    e = __builtin_fmaf(-m, q, x);
-    return __builtin_fmaf(e, y, q);
-}
 
 // th.clamp: min(max(v, lo), hi) with NaN passing through
 __device__ __forceinline__ float clampf(float v, float lo, float hi)
@@ -296,7 +251,7 @@ __device__ __forceinline__ void rotor_setpoint(const vf_dyn_cfg& c, const float*
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float d3 = c.rot_tm1sq - c.rot_4tm0 * (c.tm2 - Td[k]);
-            wd[k] = (c.one_minus_c) * (c.rot_scale * (c.rot_neg_tm1 + vf_sqrt(d3)));
+            wd[k] = (c.one_minus_c) * (c.rot_scale * (c.rot_neg_tm1 + sqrtf(d3)));
         }
     }
 }
@@ -336,21 +291,6 @@ __device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const Quat& q, c
     }
     const Quat uq{0.0f, u[0], u[1], u[2]};
     const Quat ra = qmul(qmul(q, uq), qconj(q));
-#if VF_FAST_EXACT
-    {   // wave-uniform guard: every numerator is 0 or has 2^-100 <= |x| <= 2^100; the sign of a zero quotient does not
-        // survive the "+ 0.0f" / "+ g_z" below
-        const int e0 = __builtin_amdgcn_frexp_expf(ra.x), e1 = __builtin_amdgcn_frexp_expf(ra.y), e2 = __builtin_amdgcn_frexp_expf(ra.z);
-        const int emin = min(min(e0, e1), e2);
-        const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ra.x), __builtin_fabsf(ra.y)), __builtin_fabsf(ra.z));
-        if (VF_FAST_EXACT == 2 || __builtin_amdgcn_ballot_w64(!(emin >= -99 && amax <= 0x1p100f)) == 0) {
-            const float y = 1.0f / c.m;
-            acc[0] = div_const_core(ra.x, c.m, y) + 0.0f;
-            acc[1] = div_const_core(ra.y, c.m, y) + 0.0f;
-            acc[2] = div_const_core(ra.z, c.m, y) + c.g_z;
-            return;
-        }
-    }
-#endif
     acc[0] = ra.x / c.m + 0.0f;
     acc[1] = ra.y / c.m + 0.0f;
     acc[2] = ra.z / c.m + c.g_z;
@@ -448,7 +388,7 @@ __device__ __forceinline__ void rot_substep(const vf_dyn_cfg& c, const float* tq
             aa[k] = sw[k];
         }
     }
-    const float nn = vf_sqrt(((q.w * q.w + q.x * q.x) + q.y * q.y) + q.z * q.z);   // :367, maths.py:226-230
+    const float nn = sqrtf(((q.w * q.w + q.x * q.x) + q.y * q.y) + q.z * q.z);   // :367, maths.py:226-230
     q.w = q.w / nn;
     q.x = q.x / nn;
     q.y = q.y / nn;
@@ -484,15 +424,7 @@ __device__ __forceinline__ void control_interval(const vf_dyn_cfg& c, Agent& s, 
     float Td[4], wd[4];
     desired_thrusts<ACT>(c, s, a, Td, vstrided);
     rotor_setpoint<CTRL_DELAY>(c, Td, wd);
-#if VF_SUBSTEP_UNROLL == 2
-#pragma unroll 2
-#elif VF_SUBSTEP_UNROLL == 4
-#pragma unroll 4
-#elif VF_SUBSTEP_UNROLL == 8
-#pragma unroll 8
-#else
 #pragma unroll 1
-#endif
     for (int sub = 0; sub < c.interval_steps; ++sub) {
         ck.head(sub, s);
         float ft[4];
@@ -508,45 +440,14 @@ __device__ __forceinline__ void control_interval(const vf_dyn_cfg& c, Agent& s, 
 // A step leaves ~200 B per agent dirty (13 MB at 65 536 agents).  With plain stores those lines sit in the XCD L2s until the
 // end-of-kernel release writes them back, which the NEXT launch waits for (MI355X_MICROARCH.md "boundary": + B / 6 TB/s when
 // the predecessor leaves B bytes dirty); write-through stores (sc1) push them out while the other waves still compute.
-// VF_STORE_MODE: 0 plain, 1 sc1 (write-through), 2 nt, 3 sc0 sc1 -- A/B knob of tools/env_step_probe.hip.
-#ifndef VF_STORE_MODE
-#define VF_STORE_MODE 0
-#endif
 typedef float vf_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st4(float4* p, const float4 v)
-{
-#if VF_STORE_MODE != 0
-    const vf_f4 x = {v.x, v.y, v.z, v.w};
-#endif
-#if VF_STORE_MODE == 1
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(x) : "memory");
-#elif VF_STORE_MODE == 2
-    asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(x) : "memory");
-#elif VF_STORE_MODE == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(x) : "memory");
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ void st1(float* p, const float v)
-{
-#if VF_STORE_MODE == 1
-    asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-#elif VF_STORE_MODE == 2
-    asm volatile("global_store_dword %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
-#elif VF_STORE_MODE == 3
-    asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
-#else
-    *p = v;
-#endif
-}
 
 // store with an explicit cache policy (store_rows_coalesced's MODE; measured in profiles/r04_env_quad.txt): 0 plain, 1 sc1 (write-through), 2 nt, 3 sc0 sc1
 template <int MODE>
 __device__ __forceinline__ void st4_mode(float4* p, const float4 v)
 {
     if constexpr (MODE == 0) {
-        st4(p, v);
+        *p = v;
     } else {
         const vf_f4 x = {v.x, v.y, v.z, v.w};
         if constexpr (MODE == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(x) : "memory");
@@ -557,7 +458,7 @@ __device__ __forceinline__ void st4_mode(float4* p, const float4 v)
 template <int MODE>
 __device__ __forceinline__ void st1_mode(float* p, const float v)
 {
-    if constexpr (MODE == 0) st1(p, v);
+    if constexpr (MODE == 0) *p = v;
     else if constexpr (MODE == 1) asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
     else if constexpr (MODE == 2) asm volatile("global_store_dword %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
     else asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
@@ -605,14 +506,14 @@ __device__ __forceinline__ void load_agent(float* __restrict__ S, int G, int i, 
 
 __device__ __forceinline__ void store_agent(float* __restrict__ S, int G, int i, const Agent& s, const Spares& sp)
 {
-    st4(granule(S, G, i, VF_G_POS), make_float4(s.t, s.p[0], s.p[1], s.p[2]));
-    st4(granule(S, G, i, VF_G_QUAT), make_float4(s.q.w, s.q.x, s.q.y, s.q.z));
-    st4(granule(S, G, i, VF_G_VEL), make_float4(sp.vel, s.v[0], s.v[1], s.v[2]));
-    st4(granule(S, G, i, VF_G_OMG), make_float4(sp.omg, s.w[0], s.w[1], s.w[2]));
-    st4(granule(S, G, i, VF_G_MOT), make_float4(s.wm[0], s.wm[1], s.wm[2], s.wm[3]));
-    st4(granule(S, G, i, VF_G_THR), make_float4(s.T[0], s.T[1], s.T[2], s.T[3]));
-    st4(granule(S, G, i, VF_G_AACC), make_float4(sp.aacc, s.aa[0], s.aa[1], s.aa[2]));
-    st4(granule(S, G, i, VF_G_ACC), make_float4(sp.acc, s.acc[0], s.acc[1], s.acc[2]));
+    *granule(S, G, i, VF_G_POS) = make_float4(s.t, s.p[0], s.p[1], s.p[2]);
+    *granule(S, G, i, VF_G_QUAT) = make_float4(s.q.w, s.q.x, s.q.y, s.q.z);
+    *granule(S, G, i, VF_G_VEL) = make_float4(sp.vel, s.v[0], s.v[1], s.v[2]);
+    *granule(S, G, i, VF_G_OMG) = make_float4(sp.omg, s.w[0], s.w[1], s.w[2]);
+    *granule(S, G, i, VF_G_MOT) = make_float4(s.wm[0], s.wm[1], s.wm[2], s.wm[3]);
+    *granule(S, G, i, VF_G_THR) = make_float4(s.T[0], s.T[1], s.T[2], s.T[3]);
+    *granule(S, G, i, VF_G_AACC) = make_float4(sp.aacc, s.aa[0], s.aa[1], s.aa[2]);
+    *granule(S, G, i, VF_G_ACC) = make_float4(sp.acc, s.acc[0], s.acc[1], s.acc[2]);
 }
 
 struct DynArgs {
@@ -654,7 +555,7 @@ __device__ __forceinline__ void ring_exchange_d(const DynArgs& g, int i, bool li
         const int head = g.head;
         float4* slot = granule(g.S, g.G, i, VF_G_RING + head);
         const float4 old = *slot;
-        st4(slot, an);
+        *slot = an;
         an = old;
         head_bits = __int_as_float(head + 1 == D ? 0 : head + 1);
     }
@@ -736,7 +637,7 @@ __device__ __forceinline__ void store_rows_quads(float* __restrict__ out, int N,
 #pragma unroll
     for (int k = 0; k < (16 * C + 63) / 64; ++k) {
         const int j = k * 64 + l;
-        if (j < total) st1(dst + j, tile[j]);
+        if (j < total) dst[j] = tile[j];
     }
 }
 

@@ -86,7 +86,7 @@ __device__ __forceinline__ void substep_c(const vf_dyn_cfg& c, const QuadLane& L
         x.w = x.w + sw * dt;
         x.aa = sw;
     }
-    const float nn = vf_sqrt(q_sum4(x.q * x.q));
+    const float nn = sqrtf(q_sum4(x.q * x.q));
     x.q = x.q / nn;
 }
 
@@ -109,7 +109,7 @@ __device__ __forceinline__ void control_interval_quad(const vf_dyn_cfg& c, const
     float wd_c = 0.0f;
     if constexpr (CTRL_DELAY) {      // rotor_setpoint for rotor k
         const float d3 = c.rot_tm1sq - c.rot_4tm0 * (c.tm2 - Td_c);
-        wd_c = (c.one_minus_c) * (c.rot_scale * (c.rot_neg_tm1 + vf_sqrt(d3)));
+        wd_c = (c.one_minus_c) * (c.rot_scale * (c.rot_neg_tm1 + sqrtf(d3)));
     }
     QuadState x{q_sel3(k, s.p), q_sel4(k, s.q.w, s.q.x, s.q.y, s.q.z), q_sel3(k, s.v), q_sel3(k, s.w), q_sel4(k, s.wm[0], s.wm[1], s.wm[2], s.wm[3]),
                 q_sel4(k, s.T[0], s.T[1], s.T[2], s.T[3]), q_sel3(k, s.acc), q_sel3(k, s.aa)};

@@ -463,17 +463,17 @@ int launch_env_step(vf_env* h, const float* action, const vf_env_out* out, int a
         unsigned nb = h->dyn.Npad / vf::kBlock;
         if (h->g_spawn >= 0 && auto_reset) {     // prefetched re-spawn: main blocks read copy `par`, helper blocks refill the other
             const int par = (int)((h->dyn.tick + ahead) & 1);
-            static const int mode = [] { const char* e = getenv("VISFLY_AMD_PREFETCH_MODE"); return e ? atoi(e) : 3; }();   // A/B: 1 = slot loads only, 2 = helper only
-            if (mode & 1) g.g_spawn_rd = h->g_spawn + 4 * par;
+            g.g_spawn_rd = h->g_spawn + 4 * par;
             g.g_spawn_wr = h->g_spawn + 4 * (1 - par);
-            if (mode & 2) { g.helper = (int)nb; nb += (nb + vf::kHelperSpan - 1) / vf::kHelperSpan; }
+            g.helper = (int)nb;
+            nb += (nb + vf::kHelperSpan - 1) / vf::kHelperSpan;
             // stale bits: (re)armed here when something re-spawned agents without maintaining them; not inside a stream capture
             // (the memset would replay with the graph) -- those launches run the helper's per-agent tag compare instead
             // OFF by default: they take the helper's reads from 16 to 3 B per agent-step but cost the reset regime 0.3 us per launch (two
             // atomics in every ending wave, a dependent load more in front of the helper's refills): profiles/r04_env_quad.txt
             static const bool bits_off = [] { const char* e = getenv("VISFLY_AMD_STALE_BITS"); return !(e && atoi(e) == 1); }();
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            const bool bits_wanted = h->d_stale && !bits_off && (mode & 2);
+            const bool bits_wanted = h->d_stale && !bits_off;
             if (bits_wanted) (void)hipStreamIsCapturing(st, &cap);        // (a runtime call per launch: only when the bits are on)
             if (bits_wanted && cap == hipStreamCaptureStatusNone) {
                 const int tiles = h->dyn.Npad / 64;

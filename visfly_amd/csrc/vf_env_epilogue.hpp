@@ -217,7 +217,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
     obs_row(c, s, o);
     obs_variant(e, o);
     if (live) {
-        st1(g.out.reward + i, reward);
+        g.out.reward[i] = reward;
         if (reward_reg) *reward_reg = reward;       // (callers that keep going with the agent in registers: vf_bptt_rollout.hip)
         if (done_reg) *done_reg = done;
         g.out.done[i] = done ? 1 : 0;

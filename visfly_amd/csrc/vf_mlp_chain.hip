@@ -40,8 +40,6 @@ int mlp_backward_chain_try(const vf_mlp_bwd_desc* d, const float* packed, int M,
     for (int l = 0; l < d->n_layers; ++l)
         if (!rows_fit_u32(M, d->layer[l].ld_dy)) return 0;
     const ReparamBwd rp = rpp ? *rpp : ReparamBwd{};
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
-    if (off) return 0;
     const bool launch = packed != nullptr;       // packed == nullptr: capability query only
     if (bwd_chain_matches<NetNav, true, true, false>(*d)) return launch ? bwd_chain_launch<NetNav, true, true, false>(*d, packed, M, st, rp) : 1;
     if (bwd_chain_matches<NetNav, true, false, true>(*d)) return launch ? bwd_chain_launch<NetNav, true, false, true>(*d, packed, M, st, rp) : 1;
@@ -60,8 +58,6 @@ int ppo_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const 
                          const float* in1, const float* log_std, const float* action, const float* old_lp, const float* adv,
                          const float* ret, float* part, const vf_ppo_loss_cfg* cfg, int M, hipStream_t st)
 {
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
-    if (off) return 0;
     for (int i = 0; i < d->n_layers; ++i)
         if (d->layer[i].dst < VF_MLP_OUT0 && !d->layer[i].save) return 0;          // the weight gradients need every layer input
     for (int i = 0; i < d->n_layers; ++i)
@@ -96,9 +92,8 @@ int ppo_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const 
 int mlp_forward_chain_try(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1,
                           float* out0, float* out1, int M, hipStream_t st, const ReparamFwd* rpp, const float* in2, int M_choice)
 {
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
     const ReparamFwd rp = rpp ? *rpp : ReparamFwd{};
-    if (off || (!out0 && !rp.action) || (reinterpret_cast<uintptr_t>(out0) & 15) || (reinterpret_cast<uintptr_t>(rp.action) & 15)) return 0;
+    if ((!out0 && !rp.action) || (reinterpret_cast<uintptr_t>(out0) & 15) || (reinterpret_cast<uintptr_t>(rp.action) & 15)) return 0;
     for (int i = 0; i < d->n_layers; ++i)
         if (d->layer[i].save && !rows_fit_u32(M, d->layer[i].save_ld)) return 0;
     if (!out1) {      // no value requested: the value trunk is skipped
@@ -122,8 +117,6 @@ int mlp_forward_chain_try(const vf_mlp_desc* d, const float* params, const float
 // + 16 when M rows per pass run on the 16-rows-per-wave chain
 int bwd_chain_policy_class(const vf_mlp_bwd_desc* d, int M)
 {
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
-    if (off) return 0;
     if (bwd_chain_matches<NetHover, true, false, true>(*d)) return 1 + (bwd16_ok<NetHover, true, false, true>(*d, M) ? 16 : 0);
     if (bwd_chain_matches<NetNav, true, false, true>(*d)) return 2 + (bwd16_ok<NetNav, true, false, true>(*d, M) ? 16 : 0);
     if (bwd_chain_matches<NetSacHover, true, true, true>(*d)) return 3 + (bwd16_ok<NetSacHover, true, true, true>(*d, M) ? 16 : 0);
@@ -136,8 +129,6 @@ int bwd_chain_policy_class(const vf_mlp_bwd_desc* d, int M)
 // chain16_ok apart from the row count.
 int chain16_policy_class(const vf_mlp_desc* d, const float* params)
 {
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
-    if (off) return 0;
     if (chain_matches<NetHoverPi>(*d) && chain16_ok<NetHoverPi>(*d, params, 1)) return 1;
     if (chain_matches<NetNavPi>(*d) && chain16_ok<NetNavPi>(*d, params, 1)) return 2;
     if (chain_matches<NetSacHover>(*d) && chain16_ok<NetSacHover>(*d, params, 1)) return 3;     // td_policies.Actor: mu / log_std heads
@@ -149,8 +140,6 @@ int chain16_policy_class(const vf_mlp_desc* d, const float* params)
 // vf_mlp_forward would run those M rows on the 16-rows-per-wave chain
 int chain_full_class(const vf_mlp_desc* d, const float* params, int M)
 {
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
-    if (off) return 0;
     if (chain_matches<NetHover>(*d)) return 1 + (chain16_ok<NetHover>(*d, params, M) ? 16 : 0);
     if (chain_matches<NetNav>(*d)) return 2 + (chain16_ok<NetNav>(*d, params, M) ? 16 : 0);
     return 0;

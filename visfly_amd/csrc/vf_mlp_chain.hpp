@@ -8,10 +8,6 @@
 
 #include <type_traits>
 
-#ifndef VF_CHAIN16_WT
-#define VF_CHAIN16_WT 2      // A fragments of the 16-row forward: 2 = float4 of the 32-row chain's image (hidden layers), 1 = four dwords of the
-                             // transposed image, 0 = float4 of the row-major parameter buffer (A/B)
-#endif
 #ifndef VF_CHAIN16_DEPTH
 #define VF_CHAIN16_DEPTH 24
 #endif
@@ -200,10 +196,7 @@ using NetCriticHover = ChainNet<1, 16, 8, 4, 2, 2, 2, 2, 2, true, 1, 1, 1>;   //
 // The weight fragments are BUFFER loads: descriptor over the packed image (4 SGPRs, made once) + this lane's constant 16-byte slot +
 // a scalar block offset.  r05 (tools/mfma_occupancy_probe.hip, profiles/r05_chain_split.txt): what a load costs a lone wave is its
 // ISSUE, during which the wave's dependent MFMAs cannot go -- 49 cycles per global_load with a 64-bit VGPR address (what the pointer
-// form below compiled to, plus two VALU adds), 71 with scalar base + VGPR offset, 30 as a buffer load, per item of 4 MFMAs = 256 cycles
-#ifndef VF_CHAIN_BUFFER_LOADS
-#define VF_CHAIN_BUFFER_LOADS 1
-#endif
+// form compiled to, plus two VALU adds), 71 with scalar base + VGPR offset, 30 as a buffer load, per item of 4 MFMAs = 256 cycles
 
 typedef unsigned vf_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t chain_weight_rsrc(const float* packed)
@@ -233,13 +226,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t chain_store_rsrc(unsigned long
 // and the next layer's epilogue overwrote v6 in the very next slot.  On gfx950 the exemption does not hold when the store's issue stalls
 // (first touch of freshly allocated pages): element 0 of the float4 of the last-read lanes (12-15 of every 16) went out as the NEW value
 // of v6, a pre-ReLU sum -- 8 rows x 2 floats of one saved activation wrong, once in ~3 cold launches.  With the immediate form the
-// compiler sees a store without soffset register and inserts the `s_nop 1` itself.
-#ifndef VF_CHAIN_STORE_AUX
-#define VF_CHAIN_STORE_AUX 0      // cache policy of the saved-activation / masked-gradient stores (bit 0 sc0, bit 1 nt, bit 4 sc1): A/B knob, profiles/r06_fused_tail.txt
-#endif
+// compiler sees a store without soffset register and inserts the `s_nop 1` itself.  Default cache policy: sc0 / nt / sc1 measured slower (r06).
 __device__ __forceinline__ void chain_buffer_store(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned col_off, float a, float b, float c, float d)
 {
-    __builtin_amdgcn_raw_buffer_store_b128(vf_u4{__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)}, r, (int)(lane_off + col_off), 0, VF_CHAIN_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(vf_u4{__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)}, r, (int)(lane_off + col_off), 0, 0);
 }
 
 template <class N, int I>
@@ -248,13 +238,7 @@ __device__ __forceinline__ float4 chain_load(const ChainArgs& g, int lane)
     constexpr int li = N::layer_of(I), local = I - N::first_item(li);
     constexpr ChainLayer L = N::layer(li);
     constexpr int G = N::groups(li), gq = local / L.nout, a = local % L.nout;
-#if VF_CHAIN_BUFFER_LOADS
     return chain_buffer_float4(chain_weight_rsrc(g.packed), (unsigned)lane * 16u, (unsigned)g.d.layer[L.desc].wr_off * 4u + ((L.a0 + a) * G + gq) * 1024u);
-#else
-    // wave-uniform base (scalar registers) + 32-bit lane offset: no 64-bit VGPR address arithmetic per load
-    const char* base = reinterpret_cast<const char*>(g.packed + g.d.layer[L.desc].wr_off) + ((L.a0 + a) * G + gq) * 1024;
-    return *reinterpret_cast<const float4*>(base + (unsigned)lane * 16u);
-#endif
 }
 
 // widths are compile-time (hidden layers: whole tiles; heads: 4 / 1 features in lane half 0, q = 0), so the bias loads
@@ -583,7 +567,6 @@ __device__ __forceinline__ float4 chain16_load(const ChainArgs& g, int lane)
     constexpr ChainLayer L = N::layer(li);
     constexpr int T = local / C::nout(li), a = local % C::nout(li);
     const vf_mlp_layer& D = g.d.layer[L.desc];
-#if VF_CHAIN16_WT == 2
     if constexpr (L.obs < 0) {
         // ONE float4 of the 32-row chain's own image (vf_mlp_layer.wr_off, block (a, g) = 1 KiB, lane l = n + 32 h holds
         // W[32 a + n][32 (g >> 2) + 8 (g & 3) + 4 h .. + 3]): the fragment of lane (i, kq) for output 16-tile a16, input 16-tile T is the
@@ -595,27 +578,13 @@ __device__ __forceinline__ float4 chain16_load(const ChainArgs& g, int lane)
         const char* base = reinterpret_cast<const char*>(g.packed + D.wr_off) + (blk * 1024 + 256 * (a & 1));       // wave-uniform
         return *reinterpret_cast<const float4*>(base + ((kq >> 1) * 1024u + (kq & 1u) * 512u + (unsigned)(lane & 15) * 16u));
     }
-#endif
-#if VF_CHAIN16_WT
-    {   // four dwords of the zero-padded TRANSPOSED image (vf_mlp_layer.wt_off: Wt[k][n], rows of N32 floats): a quarter-wave (16
-        // lanes n, one k) reads 64 contiguous bytes.  The float4 W[n][16 T + 4 gq ..] of the row-major parameters is one
-        // instruction instead of four, but its quarter-waves touch 16 rows each: 64 line accesses per item instead of 16
-        constexpr int N32 = N::is_head(li) ? 32 : 32 * L.nout;
-        const char* base = reinterpret_cast<const char*>(g.packed + D.wt_off + (16 * T * N32 + 16 * a));     // wave-uniform
-        const float* p = reinterpret_cast<const float*>(base + ((unsigned)(lane >> 4) * (4u * N32) + (unsigned)(lane & 15)) * 4u);
-        return make_float4(p[0], p[N32], p[2 * N32], p[3 * N32]);
-    }
-#endif
-    const int n = 16 * a + (lane & 15), gq = lane >> 4;
-    const float* w = g.params + D.w_off;
-    if constexpr (L.obs >= 0) {          // K = in_dim <= 16, rows not 16-byte aligned: guarded scalar loads
-        const float* r = w + (size_t)n * D.K;
-        const int k = 4 * gq;
-        return make_float4(k < D.K ? r[k] : 0.0f, k + 1 < D.K ? r[k + 1] : 0.0f, k + 2 < D.K ? r[k + 2] : 0.0f, k + 3 < D.K ? r[k + 3] : 0.0f);
-    } else {
-        const int nc = n < D.No ? n : D.No - 1;      // heads: rows past No repeat the last one (their outputs are never read)
-        return *reinterpret_cast<const float4*>(w + (size_t)nc * D.K + 16 * T + 4 * gq);
-    }
+    // observation layers: four dwords of the zero-padded TRANSPOSED image (vf_mlp_layer.wt_off: Wt[k][n], rows of N32 floats): a
+    // quarter-wave (16 lanes n, one k) reads 64 contiguous bytes.  The float4 W[n][16 T + 4 gq ..] of the row-major parameters is one
+    // instruction instead of four, but its quarter-waves touch 16 rows each: 64 line accesses per item instead of 16
+    constexpr int N32 = N::is_head(li) ? 32 : 32 * L.nout;
+    const char* base = reinterpret_cast<const char*>(g.packed + D.wt_off + (16 * T * N32 + 16 * a));     // wave-uniform
+    const float* p = reinterpret_cast<const float*>(base + ((unsigned)(lane >> 4) * (4u * N32) + (unsigned)(lane & 15)) * 4u);
+    return make_float4(p[0], p[N32], p[2 * N32], p[3 * N32]);
 }
 
 template <class N, int LI>

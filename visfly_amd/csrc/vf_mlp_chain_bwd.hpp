@@ -149,12 +149,7 @@ __device__ __forceinline__ float4 bwd_load(const BwdArgsChain& g, int lane)
     constexpr int oi = P::op_of(I), local = I - P::first_item(oi);
     constexpr BwdOp O = P::op(oi);
     constexpr int gq = local / O.nout, a = local % O.nout;
-#if VF_CHAIN_BUFFER_LOADS
     return chain_buffer_float4(chain_weight_rsrc(g.packed), (unsigned)lane * 16u, (unsigned)g.d.layer[P::entry(O.fl)].wq_off * 4u + ((O.a0 + a) * O.G + gq) * 1024u);
-#else
-    const char* base = reinterpret_cast<const char*>(g.packed + g.d.layer[P::entry(O.fl)].wq_off) + ((O.a0 + a) * O.G + gq) * 1024;
-    return *reinterpret_cast<const float4*>(base + (unsigned)lane * 16u);
-#endif
 }
 
 template <class P, int OI>
@@ -437,7 +432,6 @@ template <class P>
 struct Bwd16 {
     static constexpr int nin(int oi) { return P::op(oi).in_kind == 0 ? P::op(oi).G / 2 : 1; }       // 16-feature input tiles
     static constexpr int nout(int oi) { return P::op(oi).obs >= 0 ? 1 : 2 * P::op(oi).nout; }       // 16-feature output tiles
-    static constexpr int k32(int oi) { return P::op(oi).obs >= 0 ? 32 : 32 * P::op(oi).nout; }      // row length of the wb image
     static constexpr int items(int oi) { return nin(oi) * nout(oi); }
     // mask float4s (saved activations of the 16-tiles an op finalises) live in ONE register array, op oi's at mask0(oi) ..
     static constexpr int nmask(int oi)
@@ -491,30 +485,19 @@ __device__ __forceinline__ float4 bwd16_load(const BwdArgsChain& g, int lane)
     using B = Bwd16<P>;
     constexpr int oi = B::op_of(I), local = I - B::first_item(oi);
     constexpr BwdOp O = P::op(oi);
-    constexpr int T = local / B::nout(oi), a = local % B::nout(oi), K32 = B::k32(oi);
-#if VF_CHAIN16_WT == 2
-    {   // ONE float4 of the 32-row reverse chain's own image (vf_mlp_layer.wq_off, block (a, g) = 1 KiB, lane l = k + 32 h holds
-        // W[32 (g >> 2) + 8 (g & 3) + 4 h .. + 3][32 a + k]): the fragment of lane (i, kq) for output 16-tile a16, input 16-tile T is
-        // the float4 of lane 16 (a16 & 1) + i + 32 (kq & 1) in block (a16 / 2, 4 (T >> 1) + 2 (T & 1) + (kq >> 1)); quarter-waves of
-        // 256 contiguous bytes, one instruction per item (chain16_load).  Heads: component kq of lane k's float4 in block (a, 0)
-        constexpr int GQ = O.in_kind == 0 ? O.G : 1;
-        constexpr int blk = (a >> 1) * GQ + (O.in_kind == 0 ? 4 * (T >> 1) + 2 * (T & 1) : 0);
-        const unsigned kq = lane >> 4;
-        const char* qb = reinterpret_cast<const char*>(g.packed + g.d.layer[P::entry(O.fl)].wq_off) + (blk * 1024 + 256 * (a & 1));
-        if constexpr (O.in_kind == 0)
-            return *reinterpret_cast<const float4*>(qb + ((kq >> 1) * 1024u + (kq & 1u) * 512u + (unsigned)(lane & 15) * 16u));
-        else
-            return make_float4(*reinterpret_cast<const float*>(qb + ((unsigned)(lane & 15) * 16u + kq * 4u)), 0.0f, 0.0f, 0.0f);
-    }
-#endif
-    const float* base = g.packed + g.d.layer[P::entry(O.fl)].wb_off;             // wave-uniform
-    if constexpr (O.in_kind == 0) {
-        const float* p = base + (16 * T * K32 + 16 * a) + ((unsigned)(lane >> 4) * (4u * K32) + (unsigned)(lane & 15));
-        return make_float4(p[0], p[K32], p[2 * K32], p[3 * K32]);
-    } else {
-        const float* p = base + 16 * a + ((unsigned)(lane >> 4) * (unsigned)K32 + (unsigned)(lane & 15));
-        return make_float4(p[0], 0.0f, 0.0f, 0.0f);
-    }
+    constexpr int T = local / B::nout(oi), a = local % B::nout(oi);
+    // ONE float4 of the 32-row reverse chain's own image (vf_mlp_layer.wq_off, block (a, g) = 1 KiB, lane l = k + 32 h holds
+    // W[32 (g >> 2) + 8 (g & 3) + 4 h .. + 3][32 a + k]): the fragment of lane (i, kq) for output 16-tile a16, input 16-tile T is
+    // the float4 of lane 16 (a16 & 1) + i + 32 (kq & 1) in block (a16 / 2, 4 (T >> 1) + 2 (T & 1) + (kq >> 1)); quarter-waves of
+    // 256 contiguous bytes, one instruction per item (chain16_load).  Heads: component kq of lane k's float4 in block (a, 0)
+    constexpr int GQ = O.in_kind == 0 ? O.G : 1;
+    constexpr int blk = (a >> 1) * GQ + (O.in_kind == 0 ? 4 * (T >> 1) + 2 * (T & 1) : 0);
+    const unsigned kq = lane >> 4;
+    const char* qb = reinterpret_cast<const char*>(g.packed + g.d.layer[P::entry(O.fl)].wq_off) + (blk * 1024 + 256 * (a & 1));
+    if constexpr (O.in_kind == 0)
+        return *reinterpret_cast<const float4*>(qb + ((kq >> 1) * 1024u + (kq & 1u) * 512u + (unsigned)(lane & 15) * 16u));
+    else
+        return make_float4(*reinterpret_cast<const float*>(qb + ((unsigned)(lane & 15) * 16u + kq * 4u)), 0.0f, 0.0f, 0.0f);
 }
 
 template <class P, int OI>

@@ -441,8 +441,7 @@ template <class P>
 bool bwd16_ok_gen(const vf_mlp_bwd_desc& d, int M)
 {
     using Sh = typename P::Net::Shape;
-    static const int forced = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN16"); return e ? atoi(e) : -1; }();
-    if (forced == 0 || (forced < 0 && M > 16384)) return false;
+    if (M > 16384) return false;
     for (int l = 0; l < d.n_layers; ++l)
         if (d.layer[l].wb_off < 0) return false;
     for (int b = 0; b < Sh::NB; ++b)

@@ -285,12 +285,11 @@ bool chain_matches(const vf_mlp_desc& d)
 }
 
 // 16 rows per wave: only while it doubles the waves without exceeding one per SIMD (M <= 16 384), K <= 16 observation rows,
-// and the weight rows the kernel reads as float4 are 16-byte aligned.  VISFLY_AMD_MLP_CHAIN16=0/1 forces the choice (A/B).
+// and the weight rows the kernel reads as float4 are 16-byte aligned.
 template <class N>
 bool chain16_ok(const vf_mlp_desc& d, const float* params, int M)
 {
-    static const int forced = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN16"); return e ? atoi(e) : -1; }();
-    if (forced == 0 || (forced < 0 && M > 16384)) return false;
+    if (M > 16384) return false;
     if (reinterpret_cast<uintptr_t>(params) & 15) return false;
     for (int b = 0; b < N::NB; ++b)
         if (d.in_dim[b] > 16) return false;
@@ -364,15 +363,13 @@ bool bwd_chain_matches(const vf_mlp_bwd_desc& d)
 
 // 16 rows per wave for the reverse chain?  The forward's rule (chain16_ok): a small row count leaves half of the SIMDs without a
 // wave; only the policy-trunk variant with observation gradient (first-order policy optimisation, whose shards are small) is
-// instantiated.  Needs the row-major data-gradient image (wb_off) and observation widths <= 16.  VISFLY_AMD_MLP_CHAIN16=0/1
-// forces the choice (A/B) together with the forward's.
+// instantiated.  Needs the row-major data-gradient image (wb_off) and observation widths <= 16.
 template <class N, bool PI, bool VF, bool IG>
 bool bwd16_ok(const vf_mlp_bwd_desc& d, int M)
 {
     using P = BwdProg<N, PI, VF, IG>;
     if constexpr (!(IG && ((PI && !VF) || P::sac_head))) return false;      // the classes a BPTT sweep runs per step (observation gradient)
-    static const int forced = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN16"); return e ? atoi(e) : -1; }();
-    if (forced == 0 || (forced < 0 && M > 16384)) return false;
+    if (M > 16384) return false;
     for (int l = 0; l < d.n_layers; ++l)
         if (d.layer[l].wb_off < 0) return false;
     for (int b = 0; b < N::NB; ++b)

@@ -16,17 +16,11 @@
 
 namespace vf {
 
-static bool sac_off()
-{
-    static const bool off = [] { const char* e = getenv("VISFLY_AMD_MLP_CHAIN"); return e && atoi(e) == 0; }();
-    return off;
-}
-
 // 1: launched, 0: not one of the SAC actor classes (or no second output), < 0: error
 int mlp_forward_chain_try_sac(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1,
                               const float* in2, float* out0, float* out1, int M, hipStream_t st, int M_choice)
 {
-    if (sac_off() || !out0 || !out1) return 0;
+    if (!out0 || !out1) return 0;
     const ReparamFwd rp{};
     // twin critic: 1-wide heads (no alignment requirement on the outputs); the action is the input behind the extractor's
     // (over a StateTarget extractor the concatenation would be 132 wide: beyond the 128 columns every layer kernel here is built for)
@@ -40,7 +34,6 @@ int mlp_forward_chain_try_sac(const vf_mlp_desc* d, const float* params, const f
 // packed == nullptr: capability query only
 int mlp_backward_chain_try_sac(const vf_mlp_bwd_desc* d, const float* packed, int M, hipStream_t st)
 {
-    if (sac_off()) return 0;
     const bool launch = packed != nullptr;
     const ReparamBwd rp{};
     if (bwd_chain_matches<NetSacNav, true, true, true>(*d)) return launch ? bwd_chain_launch<NetSacNav, true, true, true>(*d, packed, M, st, rp) : 1;
@@ -57,7 +50,6 @@ int mlp_backward_chain_try_sac(const vf_mlp_bwd_desc* d, const float* packed, in
 int twin_q_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const float* params, const float* packed, const float* in0,
                             const float* in1, const float* target, double* part, float scale, int M, hipStream_t st)
 {
-    if (sac_off()) return 0;
     for (int i = 0; i < d->n_layers; ++i)
         if (d->layer[i].dst < VF_MLP_OUT0 && !d->layer[i].save && !((d->identity_mask >> i) & 1)) return 0;   // the weight gradients need every layer input
     for (int i = 0; i < d->n_layers; ++i)

@@ -1337,7 +1337,7 @@ __global__ __launch_bounds__(kBlock) void k_adam(float* __restrict__ p, const fl
                                                  const vf_adam_cfg c, float bc1, float bc2_sqrt)
 {
     // the first element's operands are requested ahead of the norm's reduction: they do not depend on it, and a launch this small is
-    // nothing but dependent round trips (r06: 5.1 -> see profiles/r06_fused_tail.txt)
+    // nothing but dependent round trips (r06: 5.1 us; the optimiser-step profile of round 6 under profiles/)
     const long i0 = (long)blockIdx.x * kBlock + threadIdx.x;
     float p0 = 0.0f, g0 = 0.0f, m0 = 0.0f, v0 = 0.0f;
     int4 o0 = make_int4(-1, -1, -1, -1);
@@ -1791,24 +1791,6 @@ int vf_mlp_weight_grad_layers(const vf_mlp_bwd_desc* desc, float* partials, floa
     if (!partials || !grad || M <= 0) return vf::fail(VF_EINVAL, "vf_mlp_weight_grad_layers: bad argument");
     if (int rc = check_bwd_desc(desc, "vf_mlp_weight_grad_layers")) return rc;
     return vf::mlp_wgrad_launch_layers(desc, partials, grad, M, accumulate, layer_mask, vf::as_stream(stream));
-}
-
-int vf_mlp_weight_grad_adam(const vf_mlp_bwd_desc* desc, float* partials, float* grad, int32_t M, int32_t accumulate,
-                            const vf_stats_fold* loss_stats, const vf_wgrad_tail* tail, vf_stream_t stream)
-{
-    if (!partials || !grad || !tail || M <= 0) return vf::fail(VF_EINVAL, "vf_mlp_weight_grad_adam: bad argument");
-    if (!tail->param || !tail->exp_avg || !tail->exp_avg_sq || !tail->sync || !tail->adam.sumsq_partials || tail->n <= 0 ||
-        tail->adam.step <= 0 || tail->adam.sumsq_tail_from < 0 || tail->adam.sumsq_tail_from > tail->n ||
-        (reinterpret_cast<uintptr_t>(tail->sync) & 63) || (reinterpret_cast<uintptr_t>(tail->adam.sumsq_partials) & 7))
-        return vf::fail(VF_EINVAL, "vf_mlp_weight_grad_adam: bad tail (sync: 64-byte aligned)");
-    if ((tail->adam.pack_map == nullptr) != (tail->adam.packed == nullptr))
-        return vf::fail(VF_EINVAL, "vf_mlp_weight_grad_adam: pack_map and packed must be given together");
-    if (loss_stats && (!loss_stats->part || !loss_stats->stats || loss_stats->n_rows < 1 || (reinterpret_cast<uintptr_t>(loss_stats->part) & 15)))
-        return vf::fail(VF_EINVAL, "vf_mlp_weight_grad_adam: bad loss_stats (part: 16-byte aligned rows)");
-    if (int rc = check_bwd_desc(desc, "vf_mlp_weight_grad_adam")) return rc;
-    const int rc = vf::mlp_wgrad_adam_launch(desc, partials, grad, M, accumulate, loss_stats, tail, vf::as_stream(stream));
-    if (rc < 0) return rc;
-    return rc == 1 ? VF_OK : VF_EUNSUPPORTED;      // the reason is in vf_last_error()
 }
 
 int vf_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* action, int32_t N, vf_stream_t stream)

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
             float4 an = act;
             if (c.delay_steps > 0) {
                 const int head = g.d.head;
-                st4(granule(g.d.S, Gx, i, VF_G_RING + head), an);
+                *granule(g.d.S, Gx, i, VF_G_RING + head) = an;
                 an = ring_old;
                 sp.vel = __int_as_float(head + 1 == c.delay_steps ? 0 : head + 1);
             }

@@ -19,7 +19,6 @@ Two spawn modes:
       arguments).
 """
 import ctypes as C
-import os
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -265,8 +264,8 @@ class DroneGymEnvsBase:
         self.max_episode_steps = int(max_episode_steps)
         self.max_sense_radius = 10
         self.spawn_mode = spawn
-        # persistent BPTT roll-outs also record the integrator sub-steps for the reverse launch (VISFLY_AMD_SUBSTEP_TAPE=0: A/B switch)
-        self.substep_tape = os.environ.get("VISFLY_AMD_SUBSTEP_TAPE", "1") != "0"
+        # persistent BPTT roll-outs also record the integrator sub-steps for the reverse launch (False: the reverse launch replays every interval; tests)
+        self.substep_tape = True
         self.validate_actions = (spawn == "replay") if validate_actions is None else validate_actions
         self.seed = seed
         N = self.num_agent

@@ -32,6 +32,9 @@ def _ptr(t, off=0):
 ACTIVATIONS = {"relu": 1, "tanh": 2, "elu": 3, "leaky_relu": 4}
 _TORCH_ACT = {1: "ReLU", 2: "Tanh", 3: "ELU", 4: "LeakyReLU"}
 
+# weight_grad_slots: rows per weight-gradient launch of a horizon (profiles/r06_bptt_wgrad_chunks.txt)
+WGRAD_SPLIT_ROWS = 524288
+
 
 def activation_kind(a) -> int:
     """'relu' / 'Tanh' / nn.ELU / nn.LeakyReLU() ... -> VF_ACTIVATION_*"""
@@ -196,7 +199,6 @@ class MlpPolicy:
         self._pack_map = None
         self._pi_only_ok = True
         self._fused_ppo = None             # None: untried, False: vf_ppo_update does not support this network
-        self._tail_ok, self.tail_reason = None, ""      # False: vf_mlp_weight_grad_adam declined (reason kept)
         self._fused_twin_q = None          # the same for vf_twin_q_update (a twin critic's fused update step)
         self._steps_ok, self._steps_out = None, {}      # vf_mlp_forward_steps (forward_steps)
         self._act_fused = None             # likewise for vf_mlp_forward_act
@@ -648,9 +650,8 @@ class MlpPolicy:
         assert d_value_all is None or (d_value_all.shape == (n, M, self.head_dims[1]) and d_value_all.is_contiguous())
         # one launch over 1 M rows runs at 67 TF/s, two over 512 K rows each at 76 (profiles/r06_bptt_wgrad_chunks.txt: not a cache effect --
         # the rows are as fast cold as hot): a horizon above WGRAD_SPLIT_ROWS is reduced in equal runs of whole slots, in slot order
-        cap = int(os.environ.get("VISFLY_AMD_WGRAD_SPLIT_ROWS", "524288"))
-        if n > 1 and n * M > cap > 0:
-            per = max(1, min(n - 1, cap // M))
+        if n > 1 and n * M > WGRAD_SPLIT_ROWS:
+            per = max(1, min(n - 1, WGRAD_SPLIT_ROWS // M))
             per = (n + ((n + per - 1) // per) - 1) // ((n + per - 1) // per)        # equal runs
             for s0 in range(0, n, per):
                 k = min(per, n - s0)
@@ -669,15 +670,11 @@ class MlpPolicy:
         heads and log_std -- the two gradient buckets of the two-bucket exchange (PPO.grad_buckets)"""
         return min(ly.w_off for ly in self.layers if not ly.frozen and not (ly.first or ly.src.startswith("x:") or ly.dst == "feat"))
 
-    def ppo_update(self, obs, actions, old_lp, adv, ret, loss_cfg, stats, loss_scratch, want_sumsq=False, row_index=None, tail=None,
-                   between=None):
+    def ppo_update(self, obs, actions, old_lp, adv, ret, loss_cfg, stats, loss_scratch, want_sumsq=False, row_index=None, between=None):
         """forward + PPO loss + reverse chain in one launch, then the weight gradients into ``self.grad`` (vf_ppo_update +
         vf_mlp_weight_grad).  -> False when the network is not one of the register-chained classes (the caller then
         runs forward / vf_ppo_loss / backward).  ``want_sumsq``: -> (fp64 partials tensor, count) of the squared norm of the
         gradient the fold wrote, for vf_adam_cfg.sumsq_partials (no separate grad-norm launch).
-        ``tail`` (a ``_lib.WgradTail``: parameters, Adam moments and configuration, sync words): the weight-gradient launch also folds,
-        forms the gradient norm, clips and runs Adam (vf_mlp_weight_grad_adam: the optimiser step is TWO launches) -> "adam"; when the
-        library declines (VF_EUNSUPPORTED) the call continues as ``want_sumsq`` and the caller runs vf_adam_step.
         ``between`` (callable): the weight gradients are formed in TWO launch pairs -- trunks + heads first, then the extractor MLPs -- and
         ``between()`` runs after the first pair was enqueued (the trainer starts the first bucket's all-reduce there).
         ``row_index`` (int64, M entries; vf_ppo_loss_cfg.row_index): obs / actions / old_lp / ret (and loss_cfg.old_value) are the
@@ -729,7 +726,6 @@ class MlpPolicy:
         ins = [_ptr(whole[k] if row_index is not None else b["obs:" + k]) for k in self.obs_keys] + [None] * (2 - len(self.obs_keys))
         self._pack()
         # want_sumsq: the loss-statistic rows are folded by the weight-gradient fold launch (one launch less)
-        want_sumsq = want_sumsq or tail is not None
         rc = L.vf_ppo_update(C.byref(d), C.byref(bd), _ptr(self.flat), _ptr(self._packed), ins[0], ins[1], _ptr(self.log_std),
                              _ptr(actions), _ptr(old_lp), _ptr(adv), _ptr(ret), None if want_sumsq else _ptr(stats), M,
                              C.byref(loss_cfg), _ptr(loss_scratch), st)
@@ -747,15 +743,6 @@ class MlpPolicy:
             if self._sq_part is None or self._sq_part.numel() < nb:
                 self._sq_part = th.empty(nb, dtype=th.float64, device=self.device)
             ls = _lib.StatsFold(_ptr(loss_scratch), (M + 31) // 32, 0, _ptr(stats), loss_cfg.d_log_std_out, loss_cfg.stats_accum)
-            if tail is not None and self._tail_ok is not False:
-                tail.adam.sumsq_partials = self._sq_part.data_ptr()
-                rc = L.vf_mlp_weight_grad_adam(C.byref(bd), _ptr(self._scratch), _ptr(self.grad), M, 0, C.byref(ls), C.byref(tail), st)
-                if rc == 0:
-                    return "adam"
-                if rc != _lib.EUNSUPPORTED:
-                    _lib.check(rc)
-                self._tail_ok = False          # the library said why (vf_last_error); the separate fold + Adam launches from here on
-                self.tail_reason = L.vf_last_error().decode()
             _lib.check(L.vf_mlp_weight_grad_sumsq(C.byref(bd), _ptr(self._scratch), _ptr(self.grad), M, 0, self._sq_part.data_ptr(),
                                                   C.byref(ls), st))
             return self._sq_part, nb
@@ -994,12 +981,6 @@ class PPO:
         self.num_timesteps = 0
         self._last_starts = th.ones(self.n_envs, device=dev)
         self._shuf = None
-        # fold + gradient norm + clip + Adam inside the weight-gradient launch (vf_mlp_weight_grad_adam): single-GPU steps without a
-        # target_kl check between backward and optimizer.step().  Bit-identical to the separate launches and, measured, 4.6 us per
-        # optimiser step SLOWER (two device-wide meetings of 1 000 lone waves cost 3.5 us each, the in-kernel fold reads the same 20 MB
-        # of partials, and the expensive launch boundaries are the ones behind the two big kernels, which stay:
-        # profiles/r06_fused_tail.txt) -- off unless VISFLY_AMD_FUSED_TAIL=1
-        self.fused_tail = os.environ.get("VISFLY_AMD_FUSED_TAIL", "0") == "1"
         # gradient exchange of a multi-GPU step.  1 (default): ONE all-reduce of [gradient | 16 loss statistics] between the fold and
         # Adam.  2 (VISFLY_AMD_GRAD_BUCKETS=2): the weight gradients are formed in two launch pairs -- trunks + heads, then the extractor
         # MLPs -- and the first bucket ([trunks | log_std | statistics]) is all-reduced on a second stream UNDER the second pair; the
@@ -1007,8 +988,6 @@ class PPO:
         # question for real xGMI links: 176 KB is latency, not bandwidth (bench.py prints both modes for N > 1)
         self.grad_buckets = int(os.environ.get("VISFLY_AMD_GRAD_BUCKETS", "1"))
         self._xstream, self._xev = None, None
-        self._tail_sync = th.zeros(_lib.WGRAD_SYNC_WORDS, dtype=th.int32, device=dev)
-        self._tail_launches = 0
         self.index_minibatches = False     # True: train() reads its minibatches through the permutation slice (vf_ppo_loss_cfg.row_index) instead of a shuffled copy -- measured 2 % slower, see train()
         self.logs: Dict[str, float] = {}
 
@@ -1175,12 +1154,7 @@ class PPO:
                               _ptr(mb["old_v"]) if vclip else None, self._now(self.clip_range_vf) if vclip else 0.0, 0)
         # reference-default policy shapes: forward + loss + reverse chain are one launch (vf_ppo_update)
         # single GPU: the weight-gradient fold also leaves the squared gradient norm as partial sums, which Adam adds up itself
-        tail = None
-        if self.fused_tail and self.world == 1 and self.target_kl is None:
-            pmap, packed = pol.pack_map()
-            tail = _lib.WgradTail(_ptr(pol.flat), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), pol.n_params, self._adam_cfg(self._opt_step + 1, pmap, packed, None),
-                                  self._tail_sync.data_ptr())
-        two = self.grad_buckets == 2 and tail is None and (self.world > 1 or os.environ.get("VISFLY_AMD_GRAD_BUCKETS_FORCE") == "1")
+        two = self.grad_buckets == 2 and (self.world > 1 or os.environ.get("VISFLY_AMD_GRAD_BUCKETS_FORCE") == "1")
         between = None
         if two:
             if self._xstream is None:
@@ -1192,7 +1166,7 @@ class PPO:
                 xs.wait_event(ev[0])
                 parallel.allreduce_sum_(self._gbuf[split:], stream=xs)
         res = pol.ppo_update(obs, actions, old_lp, adv, ret, cfg, self._stats, self._scratch, want_sumsq=self.world == 1 and not two,
-                             row_index=rows, tail=tail, between=between)
+                             row_index=rows, between=between)
         if two and res is True:
             ev[1].record()
             xs.wait_event(ev[1])
@@ -1201,11 +1175,6 @@ class PPO:
             th.cuda.current_stream(self.device).wait_event(ev[2])
         elif two:       # no fused step for this network: one bucket after the layer-by-layer backward (below)
             two = False
-        if res == "adam":        # the optimiser step happened inside the weight-gradient launch
-            self._opt_step += 1
-            self._tail_launches += 1
-            pol.mark_updated(packed_current=pmap is not None)
-            return self._stats
         sq = res if isinstance(res, tuple) else None
         if res is False and rows is not None:       # no fused step for this network: materialise the minibatch (what the gather did)
             obs = {k: v.index_select(0, rows) for k, v in obs.items()}
@@ -1245,14 +1214,6 @@ class PPO:
                             self.max_grad_norm if self.max_grad_norm is not None else 0.0, step, 0,
                             _ptr(pmap), _ptr(packed), None if sq is None else sq[0].data_ptr(), 0 if sq is None else sq[1],
                             self.policy.log_std_off)
-
-    def _check_tail(self):
-        """the fused optimiser tail's waves meet at device counters; one that waited past the time limit raised the abort word and the
-        update did not happen -- a hard error, reported at the trainer's next host synchronisation"""
-        if self._tail_launches and int(self._tail_sync[_lib.WGRAD_SYNC_ABORT].item()):
-            self._tail_sync.zero_()
-            raise _lib.VisflyError("the fused optimiser tail (vf_mlp_weight_grad_adam) timed out waiting for its waves to become "
-                                   "co-resident: another kernel holds part of the device; set VISFLY_AMD_FUSED_TAIL=0")
 
     def train(self, permutations=None):
         """PPO.train (PPO.py:177-337): n_epochs passes over random minibatches (SB3 RolloutBuffer.get: the trailing
@@ -1308,7 +1269,6 @@ class PPO:
             self._n_updates += 1        # PPO.py:294: once per epoch started, the early-stopped one included
             if stop:
                 break
-        self._check_tail()
         if self.world > 1:
             parallel.allreduce_sum_(stats_mb)                        # log the global means, like a single-process run would
         n_eval = len(rows_mb)
