@@ -614,7 +614,7 @@ def test_chain_backward_vs_torch_and_block_tile_kernel(M, net, mode):
 @pytest.mark.parametrize("ig", [True, False])
 def test_sac_actor_chain_vs_torch_and_block_tile_kernel(M, net, ig):
     """r04: the reference's SAC-style Actor (td_policies.py:146-252: latent_pi -> mu, log_latent_pi -> log_std, two 4-wide heads; the
-    actor of its BPTT and SHAC loops) on the register-chained kernels (vf_mlp_chain_sac.hip: forward in 32- and 16-row form, reverse
+    actor of its BPTT and SHAC loops) on the register-chained kernels (vf_mlp_chain.hip, vf_mlp_chain_reverse.hip: forward in 32- and 16-row form, reverse
     chain of both trunks with and without the observation gradient) against torch on the same weights and against the block-tile
     kernels it ran on until r03; deterministic"""
     from visfly_amd import _lib
@@ -674,7 +674,7 @@ def test_sac_actor_chain_vs_torch_and_block_tile_kernel(M, net, ig):
 @pytest.mark.parametrize("net", ["hover"])        # (over the two-branch extractor the concatenation is 132 wide: beyond the layer kernels' 128)
 def test_twin_critic_chain_vs_torch_and_block_tile_kernel(M, net):
     """r04: the reference's twin ContinuousCritic (td_policies.py:82-143: own extractor, th.cat([features, actions]) -> qf0 / qf1 -> Q;
-    68-wide first trunk layers, two 1-wide heads) on the register-chained kernels (vf_mlp_chain_sac.hip, ChainNet<.., PASS = 1>: the
+    68-wide first trunk layers, two 1-wide heads) on the register-chained kernels (vf_mlp_chain.hip, ChainNet<.., PASS = 1>: the
     action columns are one more input tile, the frozen identity layer of the table is not executed) against torch on the same weights
     and against the block-tile kernels it ran on until r03; the saved feature rows carry the action columns (the weight gradients of
     the 68-wide layers read them); deterministic"""
@@ -994,6 +994,7 @@ def test_deferred_bootstrap_equals_per_step_bootstrap(env_name):
                                             ("HoverEnv", 16401, "euler"), ("NavigationEnv", 3000, "rk4_drag"), ("HoverEnv", 16401, "rk4"),
                                             ("HoverEnv", 1000, "euler_nodelay"), ("NavigationEnv", 16500, "rk4_nodelay"),
                                             ("HoverEnv2", 3000, "euler"), ("NavigationEnv2", 3000, "euler"), ("NavigationEnv2", 16500, "rk4"),
+                                            ("NavigationEnv2", 3000, "euler_nodelay"),
                                             ("RacingEnv", 3000, "euler"), ("RacingEnv2", 3000, "euler"), ("RacingEnv2", 16401, "rk4")])
 def test_persistent_rollout_equals_the_per_step_loop(env_name, N, dyn):
     _persistent_rollout_vs_loop(env_name, N, dyn)

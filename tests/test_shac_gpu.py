@@ -334,7 +334,7 @@ def test_persistent_launches_equal_the_loop(N, H, steps, spawn):
     from visfly_amd.shac import SHAC
     from _golden import ENV_DYN
     # r05: the observation / reward variants (their adjoint is obs_variant_bwd + the NAV2 reward gradient) run SHAC on the persistent
-    # launches too -- NavigationEnv2 = the Navigation env kind under the one-observation actor (vf_bptt_*_nav2.hip)
+    # launches too -- NavigationEnv2 = the Navigation env kind under the one-observation actor (vf_bptt_*_hover.hip)
     # r06: RacingEnv2 -- the 16 gate-relative columns inside the launches (kernel-side kind VF_ENV_RACING2)
     # r06: "generated": a non-default net_arch -- actor AND twin critic are generated chain classes, the horizon runs from the actor
     # class's BPTT plugin (visfly_amd/_jit.py: PREBUILD_SAC["sac_hover"] / PREBUILD_CRITIC["critic_hover"] / PREBUILD_BPTT)

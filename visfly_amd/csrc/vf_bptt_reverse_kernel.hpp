@@ -1,6 +1,5 @@
 // vf_bptt_reverse_kernel.hpp -- k_bptt_reverse (the reverse half of a BPTT horizon as one persistent launch; scheme at the head of
-// vf_bptt_reverse.hip) + its instance table, shared by vf_bptt_reverse.hip (MlpPolicy classes) and vf_bptt_reverse_sac.hip
-// (td_policies.Actor), two translation units so that their instances compile side by side.
+// vf_bptt_reverse.hip) and the instance sets of the built-in classes (BpttReverseSet), compiled side by side in vf_bptt_reverse_*.hip.
 #pragma once
 #include "vf_env_bwd_body.hpp"
 #include "vf_mlp_chain_bwd.hpp"
@@ -163,46 +162,53 @@ __global__ __launch_bounds__(64) void k_bptt_reverse(const vf_dyn_cfg* __restric
 
 namespace vf {
 
-using RevKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::BwdArgsChain, const vf::RevArgs);
-
-// DELAY: the motor-lag form of the interval or the direct one (pick_roll, vf_bptt_rollout_kernel.hpp); the direct instances live in
-// vf_bptt_reverse_nodelay.hip
-template <class Net, int ROWS, int KIND, bool CKPT, bool DELAY>
-static RevKernel pick_rev2(const vf_dyn_cfg& c)
+// dynamic LDS of a sweep: the two sub-step tape records of the tape-reading (CKPT) instances, else the interval's parked sub-step values
+inline size_t bptt_rev_lds(bool ckpt, int S)
 {
-    using P = vf::BwdProg<Net, true, Net::HV == 4, true>;      // HV == 4: td_policies.Actor, both trunks
-    if ((c.ctrl_delay != 0) != DELAY) return nullptr;
-    if (c.integrator == VF_INT_RK4) {
-        if (c.action_type == VF_ACT_THRUST) return vf::k_bptt_reverse<P, ROWS, KIND, VF_ACT_THRUST, VF_INT_RK4, DELAY, CKPT>;
-        if (c.action_type == VF_ACT_BODYRATE) return vf::k_bptt_reverse<P, ROWS, KIND, VF_ACT_BODYRATE, VF_INT_RK4, DELAY, CKPT>;
-        return nullptr;
-    }
-    if (c.action_type == VF_ACT_THRUST) return vf::k_bptt_reverse<P, ROWS, KIND, VF_ACT_THRUST, VF_INT_EULER, DELAY, CKPT>;
-    if (c.action_type == VF_ACT_BODYRATE) return vf::k_bptt_reverse<P, ROWS, KIND, VF_ACT_BODYRATE, VF_INT_EULER, DELAY, CKPT>;
-    return nullptr;
+    return ckpt ? (size_t)2 * (S + 3) * 64 * sizeof(float4) + (64 + 256) * sizeof(float) : (size_t)S * kSave * 64 * sizeof(float);
 }
 
-// ckpt: the forward launch wrote the sub-step tape -> the instances that read it instead of replaying the interval
-template <class Net, int ROWS, int KIND, bool DELAY = true>
-static RevKernel pick_rev(const vf_dyn_cfg& c, bool ckpt)
+// the reverse halves of built-in class Net (the BPTT sweep's reverse chain: the policy trunk of an actor-critic, both trunks of the
+// SAC-style Actor) under one motor-lag form: every env kind, action type and integrator of bptt_instance (vf_env_device.hpp).
+// r16: 16 agents per wave (else 32), the rows-per-wave choice vf_mlp_backward_data makes for N rows, so that the sweep equals the
+// launch-by-launch one to the bit; ckpt: read the forward launch's sub-step tape instead of replaying the interval (16 agents per wave
+// only: the tape's records are the forward launch's waves).  One translation unit per set (vf_bptt_reverse_<class>[_nodelay].hip)
+template <class Net, bool DELAY>
+struct BpttReverseSet {
+    static int launch(int kind, const vf_dyn_cfg& c, bool r16, bool ckpt, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env, const BwdArgsChain& gb,
+                      const RevArgs& r, int N, hipStream_t st);
+};
+
+template <class Net, bool DELAY>
+int BpttReverseSet<Net, DELAY>::launch(int kind, const vf_dyn_cfg& c, bool r16, bool ckpt, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
+                                       const BwdArgsChain& gb, const RevArgs& r, int N, hipStream_t st)
 {
-    if constexpr (ROWS == 16) {          // the tape's records are the forward launch's waves: 16 agents each
-        if (ckpt) return pick_rev2<Net, ROWS, KIND, true, DELAY>(c);
-    }
-    return pick_rev2<Net, ROWS, KIND, false, DELAY>(c);
+    using P = BwdProg<Net, true, Net::HV == 4, true>;
+    const size_t lds = bptt_rev_lds(ckpt, c.interval_steps);
+    return with_env_config(kind, c, [&](auto k, auto act, auto integ, auto delay) -> int {
+        constexpr int K = decltype(k)::value, A = decltype(act)::value, I = decltype(integ)::value;
+        if constexpr (decltype(delay)::value == DELAY && bptt_instance(Net::NB, K, DELAY)) {
+            if (ckpt) hipLaunchKernelGGL((k_bptt_reverse<P, 16, K, A, I, DELAY, true>), dim3((N + 15) / 16), dim3(64), lds, st, d_dyn, d_env, gb, r);
+            else if (r16) hipLaunchKernelGGL((k_bptt_reverse<P, 16, K, A, I, DELAY, false>), dim3((N + 15) / 16), dim3(64), lds, st, d_dyn, d_env, gb, r);
+            else hipLaunchKernelGGL((k_bptt_reverse<P, 32, K, A, I, DELAY, false>), dim3((N + 31) / 32), dim3(64), lds, st, d_dyn, d_env, gb, r);
+            VF_HIP(hipGetLastError());
+            return 1;
+        } else {
+            return 0;
+        }
+    });
 }
 
-// vf_bptt_reverse_nav2.hip: the one-observation classes (net 1, 3) over the Navigation env kind (NavigationEnv2); both forms of the interval
-RevKernel pick_rev_nav2(int net, bool r16, const vf_dyn_cfg& c, bool ckpt);
-// vf_bptt_reverse_race2.hip: the one-observation classes (net 1, 3) over RacingEnv2's 16-column rows (kernel-side kind VF_ENV_RACING2)
-RevKernel pick_rev_race2(int net, bool r16, const vf_dyn_cfg& c, bool ckpt);
-// vf_bptt_reverse_nodelay.hip: every class with ctrl_delay = false (net: bwd_chain_policy_class's 1 .. 4; r16: 16 rows per wave)
-RevKernel pick_rev_nodelay(int net, bool r16, int kind, const vf_dyn_cfg& c, bool ckpt);
-
-// vf_bptt_reverse_sac.hip: net = 3 NetSacHover (Hover / Racing env), 4 NetSacNav (Navigation env); 16 rows per wave, and (r05) 32 for
-// N > 16 384 agents per launch
-RevKernel pick_rev_sac(int net, int kind, const vf_dyn_cfg& c, bool ckpt);
-RevKernel pick_rev_sac32(int net, int kind, const vf_dyn_cfg& c);
+#ifndef VF_CHAIN_PLUGIN
+extern template struct BpttReverseSet<NetHover, true>;       // vf_bptt_reverse_hover.hip
+extern template struct BpttReverseSet<NetHover, false>;      // vf_bptt_reverse_hover_nodelay.hip
+extern template struct BpttReverseSet<NetSacHover, true>;    // vf_bptt_reverse_sac.hip
+extern template struct BpttReverseSet<NetSacHover, false>;   // vf_bptt_reverse_sac_nodelay.hip
+extern template struct BpttReverseSet<NetNav, true>;         // vf_bptt_reverse_nav.hip (the state + target classes)
+extern template struct BpttReverseSet<NetNav, false>;
+extern template struct BpttReverseSet<NetSacNav, true>;
+extern template struct BpttReverseSet<NetSacNav, false>;
+#endif
 
 }  // namespace vf
 
@@ -210,7 +216,7 @@ RevKernel pick_rev_sac32(int net, int kind, const vf_dyn_cfg& c);
 namespace vf {
 
 // layout stamp of what a BPTT plugin's reverse sweep is handed (vf_chain_plugin.hpp: ChainPlugin::bptt_rev_abi)
-constexpr unsigned kBpttRevPluginAbi = 0x42560001u ^ (unsigned)(sizeof(BwdArgsChain) * 31u + sizeof(RevArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
+constexpr unsigned kBpttRevPluginAbi = 0x42560002u ^ (unsigned)(sizeof(BwdArgsChain) * 31u + sizeof(RevArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
                                                                sizeof(vf_env_cfg) * 5u);
 
 }  // namespace vf
@@ -219,7 +225,7 @@ constexpr unsigned kBpttRevPluginAbi = 0x42560001u ^ (unsigned)(sizeof(BwdArgsCh
 #include "vf_mlp_chain_gen.hpp"
 #include "vf_chain_plugin.hpp"
 extern "C" int vf_plugin_bptt_reverse(const vf_mlp_bwd_desc*, int, const vf_dyn_cfg*, const vf_dyn_cfg*, const vf_env_cfg*, const vf::BwdArgsChain*,
-                                      const void*, int, size_t, hipStream_t);
+                                      const void*, int, hipStream_t);
 #endif
 #if defined(VF_CHAIN_PLUGIN) && VF_CHAIN_PLUGIN_PART == 6
 namespace vf {
@@ -228,13 +234,15 @@ namespace vf {
 // sweep runs per step (observation gradient; both trunks for the SAC-style Actor, the policy trunk for an actor-critic)
 template <class P, int KIND, int ACT, int INTEG, bool DELAY>
 int plugin_bptt_reverse(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg* c, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
-                        const BwdArgsChain* gb, const void* rev_args, int N, size_t lds, hipStream_t st)
+                        const BwdArgsChain* gb, const void* rev_args, int N, hipStream_t st)
 {
+    const RevArgs& r = *static_cast<const RevArgs*>(rev_args);
     if (env_kind != KIND || c->action_type != ACT || c->integrator != INTEG || (c->ctrl_delay != 0) != DELAY) return 0;
+    if (!r.ck || c->delay_steps > kRingRegs) return 0;      // (the tape-reading instance only; the sweep keeps the ring's adjoints in registers)
     if (!bwd_chain_matches_gen<P>(*d, true) || !bwd16_ok_gen<P>(*d, N)) return 0;
     if (P::sac_head ? !gb->rp_ls_rows : (!gb->rp_log_std || !gb->rp_g_log_std)) return 0;
-    hipLaunchKernelGGL((k_bptt_reverse<P, 16, KIND, ACT, INTEG, DELAY, true>), dim3((N + 15) / 16), dim3(64), lds, st, d_dyn, d_env, *gb,
-                       *static_cast<const RevArgs*>(rev_args));
+    hipLaunchKernelGGL((k_bptt_reverse<P, 16, KIND, ACT, INTEG, DELAY, true>), dim3((N + 15) / 16), dim3(64), bptt_rev_lds(true, c->interval_steps),
+                       st, d_dyn, d_env, *gb, r);
     VF_HIP(hipGetLastError());
     return 1;
 }
@@ -243,11 +251,10 @@ int plugin_bptt_reverse(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg
 
 #define VF_CHAIN_PLUGIN_BPTT_DEFINE(Net, NetPi, KIND, ACT, INTEG, DELAY, NAME)                                                                  \
     extern "C" int vf_plugin_bptt_reverse(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg* c, const vf_dyn_cfg* d_dyn,                 \
-                                          const vf_env_cfg* d_env, const vf::BwdArgsChain* gb, const void* ra, int N, size_t lds,               \
-                                          hipStream_t st)                                                                                       \
+                                          const vf_env_cfg* d_env, const vf::BwdArgsChain* gb, const void* ra, int N, hipStream_t st)           \
     {                                                                                                                                           \
         using P = typename Net::template Bwd<true, Net::HV == 4, true>;                                                                         \
-        return vf::plugin_bptt_reverse<P, KIND, ACT, INTEG, DELAY>(d, env_kind, c, d_dyn, d_env, gb, ra, N, lds, st);                           \
+        return vf::plugin_bptt_reverse<P, KIND, ACT, INTEG, DELAY>(d, env_kind, c, d_dyn, d_env, gb, ra, N, st);                                \
     }
 #endif
 #if defined(VF_CHAIN_PLUGIN) && VF_CHAIN_PLUGIN_PART == 7

@@ -17,8 +17,35 @@
 //     discount recurrence in registers.
 // Everything the per-step path leaves behind -- saved activations of every slot, actions, tape rows, done flags, d_reward
 // rows, loss, episode outputs, final slab -- is bit-identical (tests/test_bptt_gpu.py), so the reverse sweep is unchanged.
+// The launch is served by the class table (vf_chain_plugin.hpp): the built-in actor classes' member below, whose kernel instances
+// are compiled in vf_bptt_rollout_<class>[_nodelay].hip, or a generated class's BPTT plugin.
 #include "vf_chain_plugin.hpp"
 #include "vf_bptt_rollout_kernel.hpp"
+
+namespace vf {
+
+// the class a horizon steps: the SAC-style Actor (both trunks), or the policy-only class of an actor-critic.  A second observation:
+// required by the state + target classes; refused by a one-observation class over the Navigation kind (NavigationEnv2) and over
+// RacingEnv2's rows, ignored over the Hover and Racing kinds
+template <class Net, class NetPi>
+int Builtin<Net, NetPi>::bptt_rollout(const vf_mlp_desc* d, const float* params, int env_kind, const vf_dyn_cfg* c, int has_target,
+                                      const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc,
+                                      const void* roll_args, int N, hipStream_t st)
+{
+    using NetR = std::conditional_t<Net::HV == 4, Net, NetPi>;
+    if (!chain_matches<NetR>(*d) || !chain16_ok<NetR>(*d, params, 1)) return 0;
+    if (NetR::NB == 2 ? !has_target : has_target && (env_kind == VF_ENV_NAV || env_kind == VF_ENV_RACING2)) return 0;
+    const EnvArgs& ge = *static_cast<const EnvArgs*>(env_args);
+    const RollArgs& r = *static_cast<const RollArgs*>(roll_args);
+    return c->ctrl_delay ? BpttRolloutSet<NetR, true>::launch(env_kind, *c, d_dyn, d_env, ge, *gc, r, N, st)
+                         : BpttRolloutSet<NetR, false>::launch(env_kind, *c, d_dyn, d_env, ge, *gc, r, N, st);
+}
+template BpttRolloutFn Builtin<NetHover, NetHoverPi>::bptt_rollout;
+template BpttRolloutFn Builtin<NetNav, NetNavPi>::bptt_rollout;
+template BpttRolloutFn Builtin<NetSacHover>::bptt_rollout;
+template BpttRolloutFn Builtin<NetSacNav>::bptt_rollout;
+
+}  // namespace vf
 
 extern "C" int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* params, const float* packed, const float* obs_slots0,
                                const float* obs_slots1, const float* log_std, const float* eps, float* actions,
@@ -40,30 +67,15 @@ extern "C" int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* 
     const int OW = race2 ? 16 : 13;
     if (desc->in_dim[0] != OW) return vf::fail(VF_EUNSUPPORTED, "vf_bptt_rollout: the first observation must be the %d-wide state row", OW);
     // (RacingEnv2: out->obs / out->terminal_obs / obs_slots0 / obs_final rows are 16 wide)
-    const int cls = vf::chain16_policy_class(desc, params);
-    // td_policies.Actor: the second head is the state-dependent log_std.  cls == 0: not a built-in class -- a generated one runs from its
-    // BPTT plugin below (visfly_amd/_jit.py: ensure_bptt), told apart by the width of the table's second head
-    bool sac = cls >= 3;
-    if (cls == 0)
-        for (int l = 0; l < desc->n_layers; ++l)
-            if (desc->layer[l].dst == VF_MLP_OUT1) sac = desc->layer[l].No == 4;
+    // td_policies.Actor: the second head is the state-dependent log_std (4 wide; an actor-critic's value head is 1 wide)
+    bool sac = false;
+    for (int l = 0; l < desc->n_layers; ++l)
+        if (desc->layer[l].dst == VF_MLP_OUT1) sac = desc->layer[l].No == 4;
     if (sac ? !log_std_rows : !log_std)
         return vf::fail(VF_EINVAL, sac ? "vf_bptt_rollout: log_std_rows (H N, 4) is required for the two-headed actor classes"
                                        : "vf_bptt_rollout: log_std is required for the state-independent-log_std classes");
     if ((reinterpret_cast<uintptr_t>(mean_rows) | reinterpret_cast<uintptr_t>(log_std_rows)) & 15)
         return vf::fail(VF_EINVAL, "vf_bptt_rollout: mean_rows / log_std_rows must be 16-byte aligned");
-    vf::RollKernel k = nullptr;
-    if (cls == 0) k = nullptr;
-    else if (race2) k = obs_slots1 ? nullptr : vf::pick_roll_race2(cls, h->dyn.cfg);
-    else if ((cls == 1 || cls == 3) && h->cfg.kind == VF_ENV_NAV) k = obs_slots1 ? nullptr : vf::pick_roll_nav2(cls, h->dyn.cfg);
-    else if (!h->dyn.cfg.ctrl_delay) k = (cls == 2 || cls == 4) && !obs_slots1 ? nullptr : vf::pick_roll_nodelay(cls, h->cfg.kind, h->dyn.cfg);
-    else if (cls == 1 && h->cfg.kind == VF_ENV_HOVER) k = vf::pick_roll<vf::NetHoverPi, VF_ENV_HOVER>(h->dyn.cfg);
-    else if (cls == 1 && h->cfg.kind == VF_ENV_RACING) k = vf::pick_roll<vf::NetHoverPi, VF_ENV_RACING>(h->dyn.cfg);
-    else if (cls == 2 && h->cfg.kind == VF_ENV_NAV && obs_slots1) k = vf::pick_roll<vf::NetNavPi, VF_ENV_NAV>(h->dyn.cfg);
-    else if (sac && (cls == 3 || obs_slots1)) k = vf::pick_roll_sac(cls, h->cfg.kind, h->dyn.cfg);
-    if (!k && cls != 0)
-        return vf::fail(VF_EUNSUPPORTED, "vf_bptt_rollout: no persistent roll-out for this network class / env kind / dynamics "
-                                         "configuration (policy trunk or td_policies.Actor over [128, 64] x [64, 64], thrust / bodyrate, Euler / RK4)");
     const int N = h->dyn.N;
     vf::EnvArgs ge{vf::DynArgs{N, h->dyn.G, h->dyn.g_drag, h->dyn.S, reinterpret_cast<const float4*>(actions), nullptr,
                                vf::ring_head(&h->dyn), nullptr, h->dyn.vel_strided},
@@ -78,24 +90,13 @@ extern "C" int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* 
                      VF_SAC_LOG_STD_MAX};
     vf::RollArgs r{H, N, tape, tape_stride, tape_done, d_reward, loss, disc, const_cast<float*>(obs_slots0), obs_final, gamma, scale, reinterpret_cast<float4*>(substep_tape), reward_rows,
                    ep_flag_rows};
-    if (k) {
-        hipLaunchKernelGGL(k, dim3((N + 15) / 16), dim3(64), 0, vf::as_stream(stream), h->dyn.d_cfg, h->d_cfg, ge, gc, r);
-        VF_HIP(hipGetLastError());
-    } else {
-        // a generated actor class: its BPTT plugin, compiled on first use for this env kind / dynamics configuration (visfly_amd/_jit.py)
-        int rc = 0;
-        const int kkind = race2 ? vf::VF_ENV_RACING2 : h->cfg.kind;
-        for (int i = 0; i < vf::chain_plugin_count() && rc == 0; ++i) {
-            const vf::ChainPlugin* p = vf::chain_plugin(i);
-            if (p->bptt_rollout && p->bptt_roll_abi == vf::kBpttRollPluginAbi)
-                rc = p->bptt_rollout(desc, params, kkind, &h->dyn.cfg, obs_slots1 != nullptr, h->dyn.d_cfg, h->d_cfg, &ge, &gc, &r, N, vf::as_stream(stream));
-        }
-        if (rc <= -1000) return vf::fail(VF_EHIP, "vf_bptt_rollout (chain plugin) failed: %s", hipGetErrorString((hipError_t)(-rc - 1000)));
-        if (rc == 0)
-            return vf::fail(VF_EUNSUPPORTED, "vf_bptt_rollout: the policy's layer table is not one of the built-in register-chained classes and no "
-                                             "BPTT plugin of a generated class serves it under this env kind / dynamics configuration");
-        vf::chain_plugin_count_launch();
-    }
+    const int rc = vf::chain_serve("vf_bptt_rollout", true, &vf::ChainPlugin::bptt_rollout, desc, params, race2 ? vf::VF_ENV_RACING2 : h->cfg.kind,
+                                   &h->dyn.cfg, obs_slots1 != nullptr, h->dyn.d_cfg, h->d_cfg, &ge, &gc, &r, N, vf::as_stream(stream));
+    if (rc < 0) return rc;
+    if (rc == 0)
+        return vf::fail(VF_EUNSUPPORTED, "vf_bptt_rollout: no persistent roll-out for this network class / env kind / dynamics configuration "
+                                         "(built in: policy trunk or td_policies.Actor over [128, 64] x [64, 64], thrust / bodyrate, Euler / RK4; "
+                                         "generated classes: through their BPTT plugin)");
     h->dyn.tick += H;
     h->stale_all = 1;       // agents re-spawned inside the launch: the prefetched copies' stale bits no longer cover them
     return VF_OK;

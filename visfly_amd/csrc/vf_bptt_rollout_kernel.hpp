@@ -1,6 +1,5 @@
 // vf_bptt_rollout_kernel.hpp -- k_bptt_rollout (the forward half of a BPTT horizon as one persistent launch; scheme at the head of
-// vf_bptt_rollout.hip) + its instance table, shared by vf_bptt_rollout.hip (state-independent log_std: the MlpPolicy classes) and
-// vf_bptt_rollout_sac.hip (td_policies.Actor: state-dependent log_std), two translation units so that their instances compile side by side.
+// vf_bptt_rollout.hip) and the instance sets of the built-in classes (BpttRolloutSet), compiled side by side in vf_bptt_rollout_*.hip.
 #pragma once
 #include "vf_env_epilogue.hpp"
 #include "vf_dyn_quad.hpp"
@@ -225,34 +224,41 @@ __global__ __launch_bounds__(64) void k_bptt_rollout(const vf_dyn_cfg* __restric
 
 namespace vf {
 
-using RollKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::EnvArgs, const vf::ChainArgs, const vf::RollArgs);
+// the forward halves of built-in class NetR (the policy-only class of an actor-critic, or the SAC-style Actor) under one motor-lag form
+// (ctrl_delay, the reference's default: envs/base/dynamics.py:510-533, or the direct form :534-554): every env kind, action type and
+// integrator of bptt_instance, 16 agents per wave.  One translation unit per set (vf_bptt_rollout_<class>[_nodelay].hip)
+template <class NetR, bool DELAY>
+struct BpttRolloutSet {
+    static int launch(int kind, const vf_dyn_cfg& c, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env, const EnvArgs& ge, const ChainArgs& gc,
+                      const RollArgs& r, int N, hipStream_t st);
+};
 
-// DELAY: the motor-lag form of the interval (ctrl_delay, the reference's default: envs/base/dynamics.py:510-533) or the direct one
-// (:534-554); the direct instances live in vf_bptt_rollout_nodelay.hip
-template <class Net, int KIND, bool DELAY = true>
-static RollKernel pick_roll(const vf_dyn_cfg& c)
+template <class NetR, bool DELAY>
+int BpttRolloutSet<NetR, DELAY>::launch(int kind, const vf_dyn_cfg& c, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env, const EnvArgs& ge,
+                                        const ChainArgs& gc, const RollArgs& r, int N, hipStream_t st)
 {
-    if ((c.ctrl_delay != 0) != DELAY) return nullptr;
-    if (c.integrator == VF_INT_RK4) {
-        if (c.action_type == VF_ACT_THRUST) return vf::k_bptt_rollout<Net, KIND, VF_ACT_THRUST, VF_INT_RK4, DELAY>;
-        if (c.action_type == VF_ACT_BODYRATE) return vf::k_bptt_rollout<Net, KIND, VF_ACT_BODYRATE, VF_INT_RK4, DELAY>;
-        return nullptr;
-    }
-    if (c.action_type == VF_ACT_THRUST) return vf::k_bptt_rollout<Net, KIND, VF_ACT_THRUST, VF_INT_EULER, DELAY>;
-    if (c.action_type == VF_ACT_BODYRATE) return vf::k_bptt_rollout<Net, KIND, VF_ACT_BODYRATE, VF_INT_EULER, DELAY>;
-    return nullptr;
+    return with_env_config(kind, c, [&](auto k, auto act, auto integ, auto delay) -> int {
+        constexpr int K = decltype(k)::value, A = decltype(act)::value, I = decltype(integ)::value;
+        if constexpr (decltype(delay)::value == DELAY && bptt_instance(NetR::NB, K, DELAY)) {
+            hipLaunchKernelGGL((k_bptt_rollout<NetR, K, A, I, DELAY>), dim3((N + 15) / 16), dim3(64), 0, st, d_dyn, d_env, ge, gc, r);
+            VF_HIP(hipGetLastError());
+            return 1;
+        } else {
+            return 0;
+        }
+    });
 }
 
-// vf_bptt_rollout_nodelay.hip: every class below with ctrl_delay = false (cls: chain16_policy_class's 1 .. 4)
-RollKernel pick_roll_nodelay(int cls, int kind, const vf_dyn_cfg& c);
-// vf_bptt_rollout_nav2.hip: the one-observation classes (1, 3) over the Navigation env kind = NavigationEnv2, whose target is inside its
-// "state" row (envs/NavigationEnv.py:163-183); both forms of the interval
-RollKernel pick_roll_nav2(int cls, const vf_dyn_cfg& c);
-
-// vf_bptt_rollout_race2.hip: the one-observation classes (1, 3) over RacingEnv2's 16-column rows (kernel-side kind VF_ENV_RACING2)
-RollKernel pick_roll_race2(int cls, const vf_dyn_cfg& c);
-// vf_bptt_rollout_sac.hip: net = 3 NetSacHover (Hover / Racing env), 4 NetSacNav (Navigation env); nullptr: no instance
-RollKernel pick_roll_sac(int net, int kind, const vf_dyn_cfg& c);
+#ifndef VF_CHAIN_PLUGIN
+extern template struct BpttRolloutSet<NetHoverPi, true>;       // vf_bptt_rollout_hover.hip
+extern template struct BpttRolloutSet<NetHoverPi, false>;      // vf_bptt_rollout_hover_nodelay.hip
+extern template struct BpttRolloutSet<NetSacHover, true>;      // vf_bptt_rollout_sac.hip
+extern template struct BpttRolloutSet<NetSacHover, false>;     // vf_bptt_rollout_sac_nodelay.hip
+extern template struct BpttRolloutSet<NetNavPi, true>;         // vf_bptt_rollout_nav.hip (the state + target classes)
+extern template struct BpttRolloutSet<NetNavPi, false>;
+extern template struct BpttRolloutSet<NetSacNav, true>;
+extern template struct BpttRolloutSet<NetSacNav, false>;
+#endif
 
 }  // namespace vf
 

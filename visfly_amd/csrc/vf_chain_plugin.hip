@@ -1,25 +1,56 @@
-// vf_chain_plugin.hip -- registry of the chain plugins (vf_chain_plugin.hpp): shared objects with the register-chained kernels of ONE
-// network shape each, compiled on first use by the host side (visfly_amd/_jit.py) for shapes libvisfly_amd.so holds no instance of.
+// vf_chain_plugin.hip -- the class table (vf_chain_plugin.hpp): the entries of the built-in classes, and the registry of the chain
+// plugins -- shared objects with the register-chained kernels of ONE network shape each, compiled on first use by the host side
+// (visfly_amd/_jit.py) for shapes libvisfly_amd.so holds no instance of.
 #include "vf_chain_plugin.hpp"
+#include "vf_ppo_rollout_kernel.hpp"
+#include "vf_bptt_rollout_kernel.hpp"
+#include "vf_bptt_reverse_kernel.hpp"
 
 #include <dlfcn.h>
 
 #include <atomic>
+#include <deque>
 #include <mutex>
 #include <string>
-#include <vector>
 
 namespace vf {
+
+// PPO: the actor-critic classes (fused PPO step, PPO roll-out); BPTT: the actor classes (a horizon's two persistent launches)
+template <class Net, class NetPi, bool PPO, bool BPTT>
+constexpr ChainPlugin builtin_entry(const char* name)
+{
+    using B = Builtin<Net, NetPi>;
+    ChainPlugin e{kChainPluginAbi, name, B::forward, B::backward, nullptr, nullptr, kRolloutPluginAbi, nullptr, kBpttRollPluginAbi,
+                  kBpttRevPluginAbi, nullptr, nullptr};
+    if constexpr (PPO) e.ppo_update = B::ppo_update, e.ppo_rollout = B::ppo_rollout;
+    if constexpr (Net::PASS != 0) e.twin_q_update = B::twin_q_update;
+    if constexpr (BPTT) e.bptt_rollout = B::bptt_rollout, e.bptt_reverse = B::bptt_reverse;
+    return e;
+}
+
+// (a layer table matches at most one class; a function-local table: a namespace-scope constant would be compiled for the device too)
+const ChainPlugin* builtin_classes()
+{
+    static const ChainPlugin t[kBuiltinClassCount] = {
+        builtin_entry<NetHover, NetHoverPi, true, true>("NetHover"),      // MlpPolicy actor-critic over StateExtractor; NetHoverPi: its policy trunk
+        builtin_entry<NetNav, NetNavPi, true, true>("NetNav"),            // ... over StateTargetExtractor
+        builtin_entry<NetSacHover, NetSacHover, false, true>("NetSacHover"),   // td_policies.Actor: mu / log_std heads
+        builtin_entry<NetSacNav, NetSacNav, false, true>("NetSacNav"),
+        builtin_entry<NetCriticHover, NetCriticHover, false, false>("NetCriticHover"),   // td_policies.ContinuousCritic
+    };
+    return t;
+}
+
 namespace {
 struct Loaded {
     std::string path;
     void* handle;
-    const ChainPlugin* p;
+    ChainPlugin p;           // the plugin's entry, less the members whose argument layout stamp is not this build's
 };
 std::mutex g_mu;
-std::vector<Loaded>& loaded()
+std::deque<Loaded>& loaded()         // (a deque: entries stay where they are while others are added)
 {
-    static std::vector<Loaded> v;
+    static std::deque<Loaded> v;
     return v;
 }
 }  // namespace
@@ -39,7 +70,7 @@ int chain_plugin_count()
 const ChainPlugin* chain_plugin(int i)
 {
     std::lock_guard<std::mutex> lk(g_mu);
-    return i >= 0 && i < (int)loaded().size() ? loaded()[i].p : nullptr;
+    return i >= 0 && i < (int)loaded().size() ? &loaded()[i].p : nullptr;
 }
 
 }  // namespace vf
@@ -61,7 +92,11 @@ extern "C" int vf_chain_plugin_load(const char* path)
         return fail(VF_EINVAL, "vf_chain_plugin_load: %s is not a chain plugin of this library build (abi %08x, expected %08x)", path,
                     p ? p->abi : 0u, kChainPluginAbi);
     }
-    loaded().push_back(Loaded{path, h, p});
+    ChainPlugin q = *p;
+    if (q.rollout_abi != kRolloutPluginAbi) q.ppo_rollout = nullptr;
+    if (q.bptt_roll_abi != kBpttRollPluginAbi) q.bptt_rollout = nullptr;
+    if (q.bptt_rev_abi != kBpttRevPluginAbi) q.bptt_reverse = nullptr;
+    loaded().push_back(Loaded{path, h, q});
     return VF_OK;
 }
 
@@ -79,7 +114,7 @@ extern "C" int vf_chain_plugin_set_enabled(int on)
 extern "C" const char* vf_chain_plugin_name(int i)
 {
     std::lock_guard<std::mutex> lk(vf::g_mu);
-    return i >= 0 && i < (int)vf::loaded().size() ? vf::loaded()[i].p->name : nullptr;
+    return i >= 0 && i < (int)vf::loaded().size() ? vf::loaded()[i].p.name : nullptr;
 }
 
 extern "C" int64_t vf_chain_plugin_launches() { return vf::g_launches.load(std::memory_order_relaxed); }

@@ -1,8 +1,12 @@
-// vf_chain_plugin.hpp -- the interface between libvisfly_amd.so and a chain plugin: a shared object, compiled on first use for one network
-// shape (visfly_amd/_jit.py), that holds the register-chained kernels of that shape (vf_mlp_chain_gen.hpp) and the three host functions
-// below.  libvisfly_amd.so loads it with vf_chain_plugin_load (include/visfly_amd.h) and asks every loaded plugin after its own classes
-// (mlp_forward_chain_try, mlp_backward_chain_try, ppo_update_chain_try).  Return values as those functions': 1 launched (or, for a
-// query, "would launch"), 0 not this plugin's shape, < 0 error (-1000 - hipError_t).
+// vf_chain_plugin.hpp -- the class table of the register-chained kernels.  An entry (ChainPlugin) serves one network class: its members
+// answer "is this call mine?" and launch the class's kernel instance if it is.  Two kinds of entry, asked in this order:
+//   * the built-in classes, compiled into libvisfly_amd.so (Builtin<Net, NetPi> below, table in vf_chain_plugin.hip): NetHover, NetNav
+//     (with their policy-only forms NetHoverPi / NetNavPi), NetSacHover, NetSacNav, NetCriticHover;
+//   * the chain plugins: shared objects, compiled on first use for one network shape (visfly_amd/_jit.py), that hold the kernels of that
+//     shape (vf_mlp_chain_gen.hpp) and the member functions below; loaded with vf_chain_plugin_load (include/visfly_amd.h).
+// Every chain entry point (mlp_forward_chain_try, mlp_backward_chain_try, ppo_update_chain_try, twin_q_update_chain_try, vf_ppo_rollout,
+// vf_bptt_rollout, vf_bptt_reverse) validates its arguments, then asks the table once through chain_serve.  Return values of a member:
+// 1 launched (or, for a query, "would launch"), 0 not this class / configuration, < 0 error (a plugin: -1000 - hipError_t).
 #pragma once
 #include "vf_mlp_chain_kernels.hpp"
 #ifdef VF_CHAIN_PLUGIN
@@ -12,46 +16,97 @@
 namespace vf {
 
 // layout stamp: both sides are compiled from the same headers; a plugin built against other struct layouts is refused
-constexpr unsigned kChainPluginAbi = 0x56460003u ^ (unsigned)(sizeof(vf_mlp_desc) * 31u + sizeof(vf_mlp_bwd_desc) * 17u + sizeof(ChainArgs) * 7u +
+constexpr unsigned kChainPluginAbi = 0x56460004u ^ (unsigned)(sizeof(vf_mlp_desc) * 31u + sizeof(vf_mlp_bwd_desc) * 17u + sizeof(ChainArgs) * 7u +
                                                             sizeof(BwdArgsChain) * 5u + sizeof(PpoRowArgs) * 3u + sizeof(ReparamFwd) + sizeof(ReparamBwd));
+
+// out1 == null: the policy-only class (no value trunk).  M_choice > 0: the rows-per-wave choice is made for M_choice rows
+// (vf_mlp_forward_steps).  in2: a third input (a plugin class has none: it answers 0)
+using ChainForwardFn = int(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1, const float* in2,
+                           float* out0, float* out1, int M, hipStream_t st, const ReparamFwd* rp, int M_choice);
+// packed == null: capability query
+using ChainBackwardFn = int(const vf_mlp_bwd_desc* d, const float* packed, int M, hipStream_t st, const ReparamBwd* rp);
+using PpoUpdateFn = int(const ChainArgs* g, const BwdArgsChain* gb, const PpoRowArgs* pr, int M, hipStream_t st);
+using TwinQUpdateFn = int(const ChainArgs* g, const BwdArgsChain* gb, const float* target, double* part, float scale, int M, hipStream_t st);
+// the persistent launches.  env_kind: the KERNEL-side kind (VF_ENV_RACING2 for RacingEnv2's 16-column rows); c: the host copy of the
+// dynamics constants; has_target: a second observation input was passed.  env_args / roll_args: vf::EnvArgs / vf::PpoRollArgs
+// (vf_ppo_rollout_kernel.hpp), vf::EnvArgs / vf::RollArgs (vf_bptt_rollout_kernel.hpp); rev_args: vf::RevArgs (vf_bptt_reverse_kernel.hpp)
+using PpoRolloutFn = int(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
+                         const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
+using BpttRolloutFn = int(const vf_mlp_desc* d, const float* params, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn,
+                          const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
+using BpttReverseFn = int(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg* c, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
+                          const BwdArgsChain* gb, const void* rev_args, int N, hipStream_t st);
 
 struct ChainPlugin {
     unsigned abi;
-    const char* name;      // the shape, for messages
-    // out1 == null: the policy-only class (no value trunk).  M_choice > 0: the rows-per-wave choice is made for M_choice rows
-    // (vf_mlp_forward_steps).  The classes a BPTT / SHAC horizon steps -- the SAC-style Actor, the policy-only class -- run 16 rows per wave
-    // where the built-in classes do (chain16_ok), so that their persistent launches (16 agents per wave) equal the per-step path to the bit
-    int (*forward)(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1, float* out0, float* out1,
-                   int M, hipStream_t st, const ReparamFwd* rp, int M_choice);
-    // packed == null: capability query
-    int (*backward)(const vf_mlp_bwd_desc* d, const float* packed, int M, hipStream_t st, const ReparamBwd* rp);
-    int (*ppo_update)(const ChainArgs* g, const BwdArgsChain* gb, const PpoRowArgs* pr, int M, hipStream_t st);
+    const char* name;      // the class / shape, for messages
+    // The classes a BPTT / SHAC horizon steps -- the SAC-style Actor, the policy-only class -- run 16 rows per wave where chain16_ok
+    // holds, so that their persistent launches (16 agents per wave) equal the per-step path to the bit
+    ChainForwardFn* forward;
+    ChainBackwardFn* backward;
+    PpoUpdateFn* ppo_update;
     // the twin critic's classes (heads (1, 1), pass-through action tile): SHAC's fused critic step (k_twin_q_update_chain); null: not a critic
-    int (*twin_q_update)(const ChainArgs* g, const BwdArgsChain* gb, const float* target, double* part, float scale, int M, hipStream_t st);
-    // a ROLL-OUT plugin (one more shared object per shape AND env kind / action type / integrator / ctrl_delay: the persistent
-    // launch of vf_ppo_rollout.hip is a template over all of them) sets only this one; env_args / roll_args: vf::EnvArgs /
-    // vf::PpoRollArgs (vf_ppo_rollout_kernel.hpp; rollout_abi stamps their layout), c: the host copy of the dynamics constants
+    TwinQUpdateFn* twin_q_update;
+    // a ROLL-OUT plugin (one more shared object per shape AND env kind / action type / integrator / ctrl_delay: the persistent launch of
+    // vf_ppo_rollout.hip is a template over all of them) sets only this one; rollout_abi stamps the layout of its arguments
     unsigned rollout_abi;
-    int (*ppo_rollout)(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
-                       const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
-    // a BPTT plugin (r06; per shape AND env kind / action type / integrator / ctrl_delay like the roll-out plugin): the two persistent
-    // launches of a BPTT / SHAC horizon for a generated actor class, 16 agents per wave -- k_bptt_rollout (vf_bptt_rollout_kernel.hpp:
-    // env_args / roll_args = vf::EnvArgs / vf::RollArgs, stamped by bptt_roll_abi) and k_bptt_reverse with the sub-step tape
-    // (vf_bptt_reverse_kernel.hpp: rev_args = vf::RevArgs, bptt_rev_abi; lds = its dynamic LDS bytes).  env_kind: the KERNEL-side kind
-    // (VF_ENV_RACING2 for RacingEnv2's 16-column rows)
+    PpoRolloutFn* ppo_rollout;
+    // a BPTT plugin (per shape AND env kind / action type / integrator / ctrl_delay like the roll-out plugin): the two persistent launches
+    // of a BPTT / SHAC horizon for an actor class -- k_bptt_rollout (bptt_roll_abi) and k_bptt_reverse (bptt_rev_abi); a generated class
+    // runs 16 agents per wave with the sub-step tape only
     unsigned bptt_roll_abi, bptt_rev_abi;
-    int (*bptt_rollout)(const vf_mlp_desc* d, const float* params, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn,
-                        const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
-    int (*bptt_reverse)(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg* c, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
-                        const BwdArgsChain* gb, const void* rev_args, int N, size_t lds, hipStream_t st);
+    BpttRolloutFn* bptt_rollout;
+    BpttReverseFn* bptt_reverse;
 };
 
-// the registry (vf_chain_plugin.hip)
+}  // namespace vf
+
+#ifndef VF_CHAIN_PLUGIN
+// ---- the library side ----
+namespace vf {
+
+// the members of built-in class Net (NetPi: its policy-only form, the class a BPTT horizon steps), each defined and instantiated in the
+// translation unit that holds its kernel instances: forward vf_mlp_chain.hip, backward vf_mlp_chain_reverse.hip, ppo_update /
+// twin_q_update vf_mlp_chain_split.hip, ppo_rollout vf_ppo_rollout.hip, bptt_rollout vf_bptt_rollout.hip, bptt_reverse vf_bptt_reverse.hip
+template <class Net, class NetPi = Net>
+struct Builtin {
+    static ChainForwardFn forward;
+    static ChainBackwardFn backward;
+    static PpoUpdateFn ppo_update;
+    static TwinQUpdateFn twin_q_update;
+    static PpoRolloutFn ppo_rollout;
+    static BpttRolloutFn bptt_rollout;
+    static BpttReverseFn bptt_reverse;
+};
+
+// the table: the built-in classes (vf_chain_plugin.hip), then the loaded plugins (registry, vf_chain_plugin.hip)
+constexpr int kBuiltinClassCount = 5;
+const ChainPlugin* builtin_classes();      // kBuiltinClassCount entries
 int chain_plugin_count();
 const ChainPlugin* chain_plugin(int i);
 void chain_plugin_count_launch();      // vf_chain_plugin_launches(): how tests see that a plugin, not the block-tile kernels, served a call
 
+// asks member `fn` of every entry of the table in order and returns the first non-zero answer; 0: nobody serves the call.  `what` names
+// the entry point in the message of a plugin's HIP error; launch: a real call, not a capability query -- counted when a plugin serves it
+template <class Fn, class... A>
+int chain_serve(const char* what, bool launch, Fn* ChainPlugin::*fn, A... a)
+{
+    auto ask = [&](const ChainPlugin& p, bool plugin) {
+        const int rc = p.*fn ? (p.*fn)(a...) : 0;
+        if (rc == 1 && launch && plugin) chain_plugin_count_launch();
+        if (rc <= -1000) return fail(VF_EHIP, "%s (chain plugin) failed: %s", what, hipGetErrorString((hipError_t)(-rc - 1000)));
+        return rc;
+    };
+    const ChainPlugin* b = builtin_classes();
+    for (int i = 0; i < kBuiltinClassCount; ++i)
+        if (int rc = ask(b[i], false)) return rc;
+    for (int i = 0, n = chain_plugin_count(); i < n; ++i)
+        if (int rc = ask(*chain_plugin(i), true)) return rc;
+    return 0;
+}
+
 }  // namespace vf
+#endif
 
 #ifdef VF_CHAIN_PLUGIN
 // ---- the plugin side: VF_CHAIN_PLUGIN_PART selects what this translation unit compiles (the parts compile in parallel) ----
@@ -59,10 +114,10 @@ void chain_plugin_count_launch();      // vf_chain_plugin_launches(): how tests 
 namespace vf {
 
 template <class Net, class NetPi>
-int plugin_forward(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1, float* out0, float* out1, int M,
-                   hipStream_t st, const ReparamFwd* rpp, int M_choice)
+int plugin_forward(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1, const float* in2, float* out0,
+                   float* out1, int M, hipStream_t st, const ReparamFwd* rpp, int M_choice)
 {
-    if (Net::NB + Net::PASS == 2 && !in1) return 0;
+    if ((Net::NB + Net::PASS == 2 && !in1) || in2) return 0;
     const ReparamFwd rp = rpp ? *rpp : ReparamFwd{};
     if (Net::PASS && (rpp || !out0 || !out1)) return 0;      // the twin critic: Q1 / Q2 (M,), no action head
     ChainArgs g{*d, params, packed, ChainIo{{in0, in1, nullptr}, out0, out1}, M, rp.log_std, reinterpret_cast<const float4*>(rp.eps),
@@ -145,7 +200,7 @@ int plugin_ppo_update(const ChainArgs* g, const BwdArgsChain* gb, const PpoRowAr
     }
 }
 
-// SHAC's fused critic step on a generated twin-critic class (vf_mlp_chain_sac.hip: twin_q_update_chain_try checked the save pointers / row counts)
+// SHAC's fused critic step on a generated twin-critic class (vf_mlp_chain.hip: twin_q_update_chain_try checked the save pointers / row counts)
 template <class Net0>
 int plugin_twin_q_update(const ChainArgs* g, const BwdArgsChain* gb, const float* target, double* part, float scale, int M, hipStream_t st)
 {
@@ -166,7 +221,8 @@ int plugin_twin_q_update(const ChainArgs* g, const BwdArgsChain* gb, const float
 
 extern "C" {
 int vf_plugin_twin_q_update(const vf::ChainArgs*, const vf::BwdArgsChain*, const float*, double*, float, int, hipStream_t);
-int vf_plugin_forward(const vf_mlp_desc*, const float*, const float*, const float*, const float*, float*, float*, int, hipStream_t, const vf::ReparamFwd*, int);
+int vf_plugin_forward(const vf_mlp_desc*, const float*, const float*, const float*, const float*, const float*, float*, float*, int, hipStream_t,
+                      const vf::ReparamFwd*, int);
 int vf_plugin_backward(const vf_mlp_bwd_desc*, const float*, int, hipStream_t, const vf::ReparamBwd*);
 int vf_plugin_ppo_update(const vf::ChainArgs*, const vf::BwdArgsChain*, const vf::PpoRowArgs*, int, hipStream_t);
 const vf::ChainPlugin* vf_chain_plugin();
@@ -176,8 +232,8 @@ const vf::ChainPlugin* vf_chain_plugin();
 #if VF_CHAIN_PLUGIN_PART == 1
 #define VF_CHAIN_PLUGIN_DEFINE(Net, NetPi, NAME)                                                                                             \
     extern "C" int vf_plugin_forward(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1,    \
-                                     float* out0, float* out1, int M, hipStream_t st, const vf::ReparamFwd* rp, int M_choice)                \
-    { return vf::plugin_forward<Net, NetPi>(d, params, packed, in0, in1, out0, out1, M, st, rp, M_choice); }
+                                     const float* in2, float* out0, float* out1, int M, hipStream_t st, const vf::ReparamFwd* rp, int M_choice) \
+    { return vf::plugin_forward<Net, NetPi>(d, params, packed, in0, in1, in2, out0, out1, M, st, rp, M_choice); }
 #elif VF_CHAIN_PLUGIN_PART == 2
 #define VF_CHAIN_PLUGIN_DEFINE(Net, NetPi, NAME)                                                                                             \
     extern "C" int vf_plugin_backward(const vf_mlp_bwd_desc* d, const float* packed, int M, hipStream_t st, const vf::ReparamBwd* rp)        \

@@ -9,6 +9,8 @@
 #include "vf_common.hpp"
 #include "vf_dyn_device.hpp"
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 namespace vf {
@@ -132,6 +134,38 @@ __device__ __forceinline__ void obs_variant(const vf_env_cfg& e, float* o)
 constexpr int VF_ENV_RACING2 = 3;
 constexpr bool kind_is_racing(int kind) { return kind == VF_ENV_RACING || kind == VF_ENV_RACING2; }
 constexpr int obs_width(int kind) { return kind == VF_ENV_RACING2 ? 16 : 13; }
+
+// the kernel-side env kinds a built-in actor class has persistent BPTT launches for (both halves): the one-observation classes over the
+// Hover, Navigation (NavigationEnv2: the target inside the "state" row) and Racing kinds, and over RacingEnv2's 16-column rows with the
+// motor lag only; the state + target classes over the Navigation kind
+constexpr bool bptt_instance(int NB, int kind, bool delay) { return NB == 2 ? kind == VF_ENV_NAV : kind != VF_ENV_RACING2 || delay; }
+
+// the persistent launches' kernels are templates over the run-time configuration: f(kind, act, integ, delay) is called with the kernel-side
+// env kind, action type, integrator and motor-lag form as std::integral_constant values.  0: an env kind / action type without instances
+// (the geometric controllers); any integrator but RK4 is Euler's
+template <class F>
+int with_env_config(int kind, const vf_dyn_cfg& c, F&& f)
+{
+    auto delay = [&](auto k, auto a, auto i) -> int {
+        return c.ctrl_delay ? f(k, a, i, std::true_type{}) : f(k, a, i, std::false_type{});
+    };
+    auto integ = [&](auto k, auto a) -> int {
+        return c.integrator == VF_INT_RK4 ? delay(k, a, std::integral_constant<int, VF_INT_RK4>{})
+                                          : delay(k, a, std::integral_constant<int, VF_INT_EULER>{});
+    };
+    auto act = [&](auto k) -> int {
+        if (c.action_type == VF_ACT_THRUST) return integ(k, std::integral_constant<int, VF_ACT_THRUST>{});
+        if (c.action_type == VF_ACT_BODYRATE) return integ(k, std::integral_constant<int, VF_ACT_BODYRATE>{});
+        return 0;
+    };
+    switch (kind) {
+    case VF_ENV_HOVER: return act(std::integral_constant<int, VF_ENV_HOVER>{});
+    case VF_ENV_NAV: return act(std::integral_constant<int, VF_ENV_NAV>{});
+    case VF_ENV_RACING: return act(std::integral_constant<int, VF_ENV_RACING>{});
+    case VF_ENV_RACING2: return act(std::integral_constant<int, VF_ENV_RACING2>{});
+    default: return 0;
+    }
+}
 // o: the raw state row [p, q, v, w] (13) -> out (16) for gate index `gate`
 __device__ __forceinline__ void race2_obs(const vf_env_cfg& e, const float* o, int gate, float* out)
 {

@@ -1,7 +1,7 @@
 // vf_mlp_chain_kernels.hpp -- the register-chained forward / reverse kernels as templates over the network class, with their layer-table
-// matchers and launchers, shared by the translation units that instantiate them: vf_mlp_chain.hip (the actor-critic classes of the
-// reference's PPO policies and the policy-only classes) and vf_mlp_chain_sac.hip (the SAC-style Actor of utils/policies/td_policies.py).
-// Two files only so that the ~2 minutes of fully unrolled code per class compile in parallel.  Scheme: see vf_mlp_chain.hip.
+// matchers and launchers, shared by the translation units that instantiate them, one per launch kind so that the fully unrolled code
+// compiles in parallel: vf_mlp_chain.hip (forward), vf_mlp_chain_reverse.hip (reverse chain), vf_mlp_chain_split.hip (the fused update
+// steps).  Scheme: see vf_mlp_chain.hip.
 #pragma once
 #include "vf_mlp_chain_bwd.hpp"
 
@@ -19,10 +19,6 @@ struct PpoRowArgs {          // per-row inputs of the fused PPO minibatch step (
 
 // the buffer row a lane's row comes from (vf_ppo_loss_cfg.row_index; one dependent load at the head of the kernel)
 __device__ __forceinline__ int ppo_source_row(const PpoRowArgs& pr, int rc) { return pr.cfg.row_index ? (int)pr.cfg.row_index[rc] : rc; }
-
-// vf_mlp_chain_split.hip: the fused update kernels with two waves per row tile; 1 launched, 0 not taken, < 0 error
-int ppo_update_split_try(const ChainArgs& g, const BwdArgsChain& gb, const void* pr, int which, int M, hipStream_t st);
-int twin_q_update_split_try(const ChainArgs& g, const BwdArgsChain& gb, const float* target, double* part, float scale, int M, hipStream_t st);
 
 template <class N>
 __global__ __launch_bounds__(64) void k_mlp_forward_chain(const ChainArgs g)

@@ -2,15 +2,16 @@
 // branch-parallel form: a workgroup of two waves per tile of 32 rows, each wave walks half of the network (vf_mlp_chain_split.hpp).
 //   k_ppo_update_split    PPO minibatch step (PPO.py:210-263) for the actor-critic classes of policies.py:18-49
 //   k_twin_q_update_split SHAC critic step (shac.py:267-270) for the twin ContinuousCritic of td_policies.py:82-143
-// Same arguments, same buffers left behind for k_mlp_wgrad as their one-wave forms (vf_mlp_chain.hip, vf_mlp_chain_sac.hip), which stay
-// the fallback (VISFLY_AMD_CHAIN_SPLIT=0 forces them: A/B).
+// Same arguments, same buffers left behind for k_mlp_wgrad as their one-wave forms k_ppo_update_chain / k_twin_q_update_chain
+// (vf_mlp_chain_kernels.hpp), which run where the split does not win (chain_split_for).  The built-in classes' members that choose
+// between the two (vf_chain_plugin.hpp: Builtin::ppo_update, Builtin::twin_q_update) live here, with all of these instances.
 #ifdef VF_SPLIT_TRACE
 #include <hip/hip_runtime.h>
 // [tile][role][32]: 0 HW_ID | XCC_ID << 32, 1 realtime at exit, 2 realtime at entry, 3 .. 7 phase stamps, 8 + 5 kind + idx: layer / op stamps
 __device__ unsigned long long vf_split_trace[2 * 8192][32];
 #define VF_CHAIN_HOOK(kind, idx) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 8192) vf_split_trace[2 * blockIdx.x + (threadIdx.x >> 6)][8 + 5 * (kind) + (idx)] = __builtin_readcyclecounter(); } while (0)
 #endif
-#include "vf_mlp_chain_kernels.hpp"
+#include "vf_chain_plugin.hpp"
 #include "vf_mlp_chain_split.hpp"
 
 namespace vf {
@@ -138,19 +139,19 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     else ppo_update_role<N, 1>(g, gb, pr);
 }
 
-// 1 launched, 0 not taken (class, switch), < 0 error.  Called by ppo_update_chain_try after ITS checks of the tables (row counts, saved
-// copies); part: ceil(M / 32) x kStats floats
-int ppo_update_split_try(const ChainArgs& g, const BwdArgsChain& gb, const void* prv, int which, int M, hipStream_t st)
+// the fused PPO step of an actor-critic class (ppo_update_chain_try checked the row counts and saved copies); pr->part: ceil(M / 32) x kStats
+template <class Net, class NetPi>
+int Builtin<Net, NetPi>::ppo_update(const ChainArgs* g, const BwdArgsChain* gb, const PpoRowArgs* pr, int M, hipStream_t st)
 {
-    if (!chain_split_for(M)) return 0;
-    const PpoRowArgs& pr = *static_cast<const PpoRowArgs*>(prv);
+    if ((Net::NB == 2 && !g->io.in[1]) || !chain_matches<Net>(g->d) || !bwd_chain_matches<Net, true, true, false>(gb->d)) return 0;
     const dim3 grid((M + 31) / 32);
-    if (which == 2) hipLaunchKernelGGL(k_ppo_update_split<NetNav>, grid, dim3(128), 0, st, g, gb, pr);
-    else if (which == 1) hipLaunchKernelGGL(k_ppo_update_split<NetHover>, grid, dim3(128), 0, st, g, gb, pr);
-    else return 0;
+    if (chain_split_for(M)) hipLaunchKernelGGL(k_ppo_update_split<Net>, grid, dim3(128), 0, st, *g, *gb, *pr);
+    else hipLaunchKernelGGL(k_ppo_update_chain<Net>, grid, dim3(64), 0, st, *g, *gb, *pr);
     VF_HIP(hipGetLastError());
     return 1;
 }
+template PpoUpdateFn Builtin<NetHover, NetHoverPi>::ppo_update;
+template PpoUpdateFn Builtin<NetNav, NetNavPi>::ppo_update;
 
 // ------------------------------------------------------------------------------------------------
 template <class N, int R>
@@ -207,13 +208,19 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     else twin_q_update_role<N, 1>(g, gb, target, part, scale);
 }
 
-int twin_q_update_split_try(const ChainArgs& g, const BwdArgsChain& gb, const float* target, double* part, float scale, int M, hipStream_t st)
+// SHAC's fused critic step on the twin critic's class (twin_q_update_chain_try checked the row counts and saved copies); part: ceil(M / 32) doubles
+template <class Net, class NetPi>
+int Builtin<Net, NetPi>::twin_q_update(const ChainArgs* g, const BwdArgsChain* gb, const float* target, double* part, float scale, int M,
+                                       hipStream_t st)
 {
-    if (!chain_split_for(M)) return 0;
-    hipLaunchKernelGGL(k_twin_q_update_split<NetCriticHover>, dim3((M + 31) / 32), dim3(128), 0, st, g, gb, target, part, scale);
+    if (!g->io.in[1] || !chain_matches<Net>(g->d) || !bwd_chain_matches<Net, true, true, false>(gb->d)) return 0;
+    const dim3 grid((M + 31) / 32);
+    if (chain_split_for(M)) hipLaunchKernelGGL(k_twin_q_update_split<Net>, grid, dim3(128), 0, st, *g, *gb, target, part, scale);
+    else hipLaunchKernelGGL(k_twin_q_update_chain<Net>, grid, dim3(64), 0, st, *g, *gb, target, part, scale);
     VF_HIP(hipGetLastError());
     return 1;
 }
+template TwinQUpdateFn Builtin<NetCriticHover>::twin_q_update;
 
 }  // namespace vf
 

@@ -16,31 +16,38 @@
 #include "vf_chain_plugin.hpp"
 #include "vf_ppo_rollout_kernel.hpp"
 
-namespace {
+namespace vf {
 
-using PpoRollKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::EnvArgs, const vf::ChainArgs, const vf::PpoRollArgs);
-
-template <class Net, int ROWS, int KIND, bool DELAY>
-PpoRollKernel pick_ppo_roll2(const vf_dyn_cfg& c)
+// the roll-out of an actor-critic class (vf_chain_plugin.hpp: Builtin::ppo_rollout): the one-observation class over the Hover and
+// Navigation kinds (NavigationEnv2: the target is inside the "state" row) with either form of the interval, over RacingEnv's raw row and
+// RacingEnv2's 16 gate-relative columns (kernel-side kind VF_ENV_RACING2) with the motor lag; the state + target class over the
+// Navigation kind.  ROWS: the rows-per-wave choice of vf_mlp_forward for N rows (chain16_ok), so that the heads are the per-step path's
+// to the bit
+template <class Net, class NetPi>
+int Builtin<Net, NetPi>::ppo_rollout(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn,
+                                     const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st)
 {
-    if (c.integrator == VF_INT_RK4) {      // BASELINE configs[2]'s dynamics (utils/maths.py:353-386, repaired): bodyrate; thrust too
-        if (c.action_type == VF_ACT_THRUST) return vf::k_ppo_rollout<Net, ROWS, KIND, VF_ACT_THRUST, VF_INT_RK4, DELAY>;
-        if (c.action_type == VF_ACT_BODYRATE) return vf::k_ppo_rollout<Net, ROWS, KIND, VF_ACT_BODYRATE, VF_INT_RK4, DELAY>;
-        return nullptr;
-    }
-    if (c.action_type == VF_ACT_THRUST) return vf::k_ppo_rollout<Net, ROWS, KIND, VF_ACT_THRUST, VF_INT_EULER, DELAY>;
-    if (c.action_type == VF_ACT_BODYRATE) return vf::k_ppo_rollout<Net, ROWS, KIND, VF_ACT_BODYRATE, VF_INT_EULER, DELAY>;
-    return nullptr;
+    if (!chain_matches<Net>(*d) || (Net::NB == 2 ? !has_target : has_target && env_kind != VF_ENV_HOVER)) return 0;
+    const bool r16 = chain16_ok<Net>(*d, gc->params, N);
+    const EnvArgs& ge = *static_cast<const EnvArgs*>(env_args);
+    const PpoRollArgs& r = *static_cast<const PpoRollArgs*>(roll_args);
+    return with_env_config(env_kind, *c, [&](auto kind, auto act, auto integ, auto delay) -> int {
+        constexpr int K = decltype(kind)::value, A = decltype(act)::value, I = decltype(integ)::value;
+        constexpr bool D = decltype(delay)::value;
+        if constexpr (Net::NB == 2 ? K == VF_ENV_NAV : K == VF_ENV_HOVER || K == VF_ENV_NAV || D) {
+            if (r16) hipLaunchKernelGGL((k_ppo_rollout<Net, 16, K, A, I, D>), dim3((N + 15) / 16), dim3(64), 0, st, d_dyn, d_env, ge, *gc, r);
+            else hipLaunchKernelGGL((k_ppo_rollout<Net, 32, K, A, I, D>), dim3((N + 31) / 32), dim3(64), 0, st, d_dyn, d_env, ge, *gc, r);
+            VF_HIP(hipGetLastError());
+            return 1;
+        } else {
+            return 0;
+        }
+    });
 }
+template PpoRolloutFn Builtin<NetHover, NetHoverPi>::ppo_rollout;
+template PpoRolloutFn Builtin<NetNav, NetNavPi>::ppo_rollout;
 
-// motor lag (ctrl_delay, the reference's default) or the direct form of the interval (envs/base/dynamics.py:510-554; r05)
-template <class Net, int ROWS, int KIND>
-PpoRollKernel pick_ppo_roll(const vf_dyn_cfg& c)
-{
-    return c.ctrl_delay ? pick_ppo_roll2<Net, ROWS, KIND, true>(c) : pick_ppo_roll2<Net, ROWS, KIND, false>(c);
-}
-
-}  // namespace
+}  // namespace vf
 
 extern "C" int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* params, const float* packed, const vf_ppo_rollout_args* a,
                               vf_stream_t stream)
@@ -61,26 +68,11 @@ extern "C" int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* p
     if ((reinterpret_cast<uintptr_t>(a->means) | reinterpret_cast<uintptr_t>(a->actions) | reinterpret_cast<uintptr_t>(a->stat)) & 15)
         return vf::fail(VF_EINVAL, "vf_ppo_rollout: means / actions / stat must be 16-byte aligned");
     const int N = h->dyn.N, T = a->T;
-    // the rows-per-wave choice of vf_mlp_forward for N rows (chain16_ok), so that the heads are the per-step path's to the bit
-    const int cls = vf::chain_full_class(desc, params, N);        // 0 none; 1 NetHover, 2 NetNav; + 16 when the 16-row chain runs N rows
-    const bool r16 = (cls & 16) != 0;
-    PpoRollKernel k = nullptr;
-    if ((cls & 15) == 1 && h->cfg.kind == VF_ENV_HOVER)
-        k = r16 ? pick_ppo_roll<vf::NetHover, 16, VF_ENV_HOVER>(h->dyn.cfg) : pick_ppo_roll<vf::NetHover, 32, VF_ENV_HOVER>(h->dyn.cfg);
-    else if ((cls & 15) == 2 && h->cfg.kind == VF_ENV_NAV && a->obs_target)
-        k = r16 ? pick_ppo_roll<vf::NetNav, 16, VF_ENV_NAV>(h->dyn.cfg) : pick_ppo_roll<vf::NetNav, 32, VF_ENV_NAV>(h->dyn.cfg);
-    else if ((cls & 15) == 1 && h->cfg.kind == VF_ENV_NAV && !a->obs_target)      // NavigationEnv2: the target is inside the "state" row
-        k = r16 ? pick_ppo_roll<vf::NetHover, 16, VF_ENV_NAV>(h->dyn.cfg) : pick_ppo_roll<vf::NetHover, 32, VF_ENV_NAV>(h->dyn.cfg);
-    // r06: RacingEnv (the raw state row) and RacingEnv2 (obs_mode VF_OBS_RACE2: the 16 gate-relative columns of the agent's current gate,
-    // formed by the epilogue -- kernel-side kind VF_ENV_RACING2) under the one-observation class; the motor-lag form of the interval
-    const bool race2 = h->cfg.kind == VF_ENV_RACING && h->cfg.obs_mode == VF_OBS_RACE2;
+    const bool race2 = h->cfg.kind == VF_ENV_RACING && h->cfg.obs_mode == VF_OBS_RACE2;      // RacingEnv2: 16 gate-relative columns
     const int OW = race2 ? 16 : 13;
-    if (desc->in_dim[0] != OW) k = nullptr;
-    else if ((cls & 15) == 1 && h->cfg.kind == VF_ENV_RACING && !a->obs_target && h->dyn.cfg.ctrl_delay) {
-        if (race2) k = r16 ? pick_ppo_roll2<vf::NetHover, 16, vf::VF_ENV_RACING2, true>(h->dyn.cfg) : pick_ppo_roll2<vf::NetHover, 32, vf::VF_ENV_RACING2, true>(h->dyn.cfg);
-        else k = r16 ? pick_ppo_roll2<vf::NetHover, 16, VF_ENV_RACING, true>(h->dyn.cfg) : pick_ppo_roll2<vf::NetHover, 32, VF_ENV_RACING, true>(h->dyn.cfg);
-    }
-    const int rows = r16 ? 16 : 32;
+    // (a class padded to the same 16 input columns would match 13- and 16-wide rows alike: only the width the env kind's epilogue forms)
+    if (desc->in_dim[0] != OW)
+        return vf::fail(VF_EUNSUPPORTED, "vf_ppo_rollout: the first observation must be the %d-wide state row", OW);
     vf::EnvArgs ge{vf::DynArgs{N, h->dyn.G, h->dyn.g_drag, h->dyn.S, nullptr, nullptr, vf::ring_head(&h->dyn), nullptr, h->dyn.vel_strided},
                    *out, h->g_race, 1};
     ge.out.done_list = ge.out.done_count = nullptr;
@@ -90,26 +82,13 @@ extern "C" int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* p
     vf::PpoRollArgs r{T, N, reinterpret_cast<float4*>(a->actions), a->log_probs, a->rewards, a->episode_starts, a->last_starts,
                       a->obs_state, a->obs_final, a->log_std, a->noise_key, a->sample_step, a->obs_target_row, a->w1, a->capacity, a->cursor,
                       a->idx_list, a->rows0, a->rows1, a->stat};
-    if (k) {
-        hipLaunchKernelGGL(k, dim3((N + rows - 1) / rows), dim3(64), 0, vf::as_stream(stream), h->dyn.d_cfg, h->d_cfg, ge, gc, r);
-        VF_HIP(hipGetLastError());
-    } else {
-        // a generated class: its roll-out plugin, compiled on first use for this env kind / dynamics configuration (visfly_amd/_jit.py)
-        int rc = 0;
-        // (only for the observation width the env kind's epilogue forms: a class padded to the same 16 input columns matches 13- and 16-wide rows alike)
-        for (int i = 0; i < vf::chain_plugin_count() && rc == 0 && desc->in_dim[0] == OW; ++i) {
-            const vf::ChainPlugin* p = vf::chain_plugin(i);
-            if (p->ppo_rollout && p->rollout_abi == vf::kRolloutPluginAbi)
-                rc = p->ppo_rollout(desc, race2 ? vf::VF_ENV_RACING2 : h->cfg.kind, &h->dyn.cfg, a->obs_target != nullptr, h->dyn.d_cfg, h->d_cfg,
-                                    &ge, &gc, &r, N, vf::as_stream(stream));      // (the KERNEL-side kind: RacingEnv2's 16 columns are formed by the epilogue)
-        }
-        if (rc <= -1000) return vf::fail(VF_EHIP, "vf_ppo_rollout (chain plugin) failed: %s", hipGetErrorString((hipError_t)(-rc - 1000)));
-        if (rc == 0)
-            return vf::fail(VF_EUNSUPPORTED, "vf_ppo_rollout: no persistent roll-out for this network class / env kind / dynamics "
-                                             "configuration (built in: [128, 64] x [64, 64] actor-critic, Hover / Navigation, thrust / bodyrate, "
-                                             "Euler / RK4; generated classes: through their roll-out plugin)");
-        vf::chain_plugin_count_launch();
-    }
+    const int rc = vf::chain_serve("vf_ppo_rollout", true, &vf::ChainPlugin::ppo_rollout, desc, race2 ? vf::VF_ENV_RACING2 : h->cfg.kind, &h->dyn.cfg,
+                                   a->obs_target != nullptr, h->dyn.d_cfg, h->d_cfg, &ge, &gc, &r, N, vf::as_stream(stream));
+    if (rc < 0) return rc;
+    if (rc == 0)
+        return vf::fail(VF_EUNSUPPORTED, "vf_ppo_rollout: no persistent roll-out for this network class / env kind / dynamics "
+                                         "configuration (built in: [128, 64] x [64, 64] actor-critic, Hover / Navigation / Racing, thrust / "
+                                         "bodyrate, Euler / RK4; generated classes: through their roll-out plugin)");
     h->dyn.tick += T;
     h->stale_all = 1;       // agents re-spawned inside the launch: the prefetched copies' stale bits no longer cover them
     return VF_OK;
