@@ -295,6 +295,18 @@ int64_t vf_env_slab_floats(const vf_env* h);
 int vf_env_bind(vf_env* h, float* slab);
 vf_dyn* vf_env_dyn(vf_env* h);   /* embedded dynamics handle sharing the slab (DroneEnvsBase.dynamics) */
 
+/* Global agent ids (additive within ABI 11).  Every random stream the device keys by agent -- the spawner and the drag
+ * domain-randomisation draws (Philox counter {agent, episode#, k}), the exploration noise of vf_ppo_rollout (counter {row, step}) --
+ * uses first_agent + i for row i of this handle.  A handle that holds rows [first, first + N) of a larger population then draws,
+ * bit for bit, what those rows of ONE handle over the whole population draw with the same seed: a run can be sharded over ranks
+ * (or re-sharded) without becoming a different experiment.  Default 0 = rows are their own ids, the behaviour before this call
+ * existed.  first_agent >= 0 and first_agent + N <= 2^32 (the counter word is 32 bits), else VF_EINVAL.  Rewrites the handle's
+ * device constant block in place after a device-wide synchronisation and invalidates the prefetched re-spawn copies (drawn
+ * for the old ids); meant to be called once, before the first reset.  The stand-alone samplers take the same id as an argument:
+ * vf_head_sample_at, vf_noise_fill. */
+int vf_env_set_agent_offset(vf_env* h, int64_t first_agent);
+int64_t vf_env_agent_offset(const vf_env* h);   /* the value set, 0 by default; -1 for a null handle */
+
 /* Time-varying / per-agent wind (envs/base/dynamics.py:132-174,384-388: wind_settings given as strings are eval'ed into
  * functions of (t, previous wind) and re-evaluated by update_wind() at the top of every step; the value then holds for the
  * whole control interval and enters p' = v + wind and the velocity observation, :751-752).  The functions themselves are host
@@ -724,6 +736,16 @@ int vf_bptt_accumulate_checkpoint(const float* reward, const uint8_t* done, floa
  * Philox4x32-10 keyed by (seed, row, step); log_prob as SB3 computes it.  deterministic != 0: a = tanh(mean). */
 int vf_head_sample(const float* mean, const float* log_std, float* action, float* log_prob, int32_t M,
                    uint64_t seed, uint64_t step, int32_t deterministic, vf_stream_t stream);
+/* the same with Philox counter row row0 + i for row i (vf_head_sample: row0 = 0): the rows of a shard whose first global agent id is
+ * row0 (vf_env_set_agent_offset).  row0 + M <= 2^32. */
+int vf_head_sample_at(const float* mean, const float* log_std, float* action, float* log_prob, int32_t M, uint64_t row0,
+                      uint64_t seed, uint64_t step, int32_t deterministic, vf_stream_t stream);
+/* Per-agent standard-normal rows for the trainers that take their exploration noise as a tensor (BPTT, SHAC):
+ * eps[t][i][0..3] (T x N x 4 floats, 16-byte aligned) = the four Box-Muller normals of ONE Philox4x32-10 block with counter
+ * {row0 + i, step0 + t} and key `seed` -- the arithmetic of vf_head_sample's noise under a domain tag of its own, so the two
+ * streams never coincide.  A function of (seed, global row, step) alone: any [row0, row0 + n) window of any fill holds the same
+ * bits.  One 16-byte store per (t, agent).  1 <= T <= 65535, row0 + N <= 2^32. */
+int vf_noise_fill(float* eps, int32_t T, int32_t N, uint64_t row0, uint64_t seed, uint64_t step0, vf_stream_t stream);
 
 typedef struct vf_ppo_loss_cfg {
     float clip_range, ent_coef, vf_coef;

@@ -105,9 +105,23 @@ class BPTT:
         self._sumsq, self._scratch = th.zeros(1, device=self.device), th.zeros(4096, device=self.device)
         self.seed = seed
         self._gen = th.Generator(device=self.device).manual_seed(int(seed) + 1000003 * self.rank)
+        # over a globally keyed env (envs/base.py: agent_offset) the per-agent exploration noise is vf_noise_fill's stream instead:
+        # a function of (seed, agent_offset + row, step) alone, the same on every rank.  _noise_step counts the rows drawn so far
+        self._row0 = getattr(env, "agent_offset", None)
+        self._noise_step = 0
         self._opt_step = 0
         self.num_timesteps = 0
         self.logs: Dict[str, float] = {}
+
+    def _noise(self, T, N):
+        """(T, N, 4) standard normals: exploration noise of T consecutive steps of N agents"""
+        if self._row0 is None:
+            return th.randn((T, N, 4), device=self.device, generator=self._gen)
+        eps = th.empty((T, N, 4), dtype=th.float32, device=self.device)
+        _lib.check(_lib.lib().vf_noise_fill(_lib.ptr(eps), T, N, self._row0, int(self.seed) & (2 ** 64 - 1), self._noise_step,
+                                            _lib.current_stream(self.device)))
+        self._noise_step += T
+        return eps
 
     def _make_reference_actor(self, obs, policy_kwargs, seed):
         """td_policies.Actor (:146-252): extractor -> (latent_pi -> mu | log_latent_pi -> log_std); nn.Linear default initialisation
@@ -191,7 +205,7 @@ class BPTT:
         defer = self._defer_wgrad
         f = dict(dtype=th.float32, device=dev)
         disc, loss_vec = th.ones(N, **f), th.zeros(N, **f)
-        eps = self._eps_override if self._eps_override is not None else th.randn((H, N, 4), device=dev, generator=self._gen)
+        eps = self._eps_override if self._eps_override is not None else self._noise(H, N)
         assert eps.shape == (H, N, 4)
         acts, drews = th.empty((H, N, 4), **f), th.empty((H, N), **f)
         ls_rows = pol._slot_blocks[N][1]["value"]                                      # (slots, N, 4): slot t's log_std head
@@ -229,6 +243,7 @@ class BPTT:
             g_obs = d_in.get("state") if t > 0 else None
         if defer:
             pol.weight_grad_slots(N, H, d_mus, accumulate=True, d_value_all=d_lss)
+        self._horizon = dict(actions=acts, loss_vec=loss_vec)       # per-agent rows of the last horizon (tests, diagnostics)
         return loss_vec.mean() / self.world
 
     def _grad_reverse_sweep(self):
@@ -256,7 +271,7 @@ class BPTT:
         obs = env.get_observation()
         # per-horizon buffers in one allocation each; the exploration noise of the whole horizon is one draw
         acts, drews = th.empty((H, N, 4), device=dev), th.empty((H, N), device=dev)
-        epss = th.randn((H, N, 4), device=dev, generator=self._gen)
+        epss = self._noise(H, N)
         ckpt_done = False
         fused = False
         if defer and self.fused_rollout and pol._act_fused is not False:
@@ -298,6 +313,7 @@ class BPTT:
         if defer:
             pol.weight_grad_slots(N, H, d_means, accumulate=True)
         pol.grad[pol.log_std_off:] = g_ls_rows.sum(dim=(0, 1)) if defer else g_ls.sum(dim=0)
+        self._horizon = dict(actions=acts, loss_vec=loss_vec)       # per-agent rows of the last horizon (tests, diagnostics)
         return loss_vec.mean() / self.world
 
     def _grad_autograd(self):
@@ -313,7 +329,7 @@ class BPTT:
         disc = th.ones(N, device=self.device)
         loss_vec = th.zeros(N, device=self.device)
         obs = env.get_observation()
-        epss = th.randn((self.H, N, 4), device=self.device, generator=self._gen)     # same draw as the reverse sweep
+        epss = self._noise(self.H, N)     # same draw as the reverse sweep
         for t in range(self.H):
             mean = PolicyFunction.apply(pol, self.obs_keys, anchor, *[obs[k] for k in self.obs_keys])
             action = th.tanh(mean + log_std.exp() * epss[t])     # reparameterised squashed Gaussian (td_policies Actor)
@@ -348,7 +364,7 @@ class BPTT:
             mu, ls = self.policy.forward({k: obs[k].detach().contiguous() for k in self.obs_keys}, save_activations=False, slot=self.H + 1)
             if deterministic:
                 return th.tanh(mu), None
-            eps = th.randn((N, 4), device=self.device, generator=self._gen)
+            eps = self._noise(1, N)[0]
             action = th.empty((N, 4), device=self.device)
             self._head_fwd(mu, ls.contiguous(), eps, action)
             return action, None
@@ -356,7 +372,7 @@ class BPTT:
                                       slot=self.H + 1, need_value=False)
         if deterministic:
             return th.tanh(mean), None
-        eps = th.randn((N, 4), device=self.device, generator=self._gen)
+        eps = self._noise(1, N)[0]
         return th.tanh(mean + self.policy.log_std.exp() * eps), None
 
     # ---- checkpoints ----
@@ -366,6 +382,7 @@ class BPTT:
     def _state(self):
         return {"actor": self.policy.flat.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
                 "opt_step": int(self._opt_step), "num_timesteps": int(self.num_timesteps), "rng": self._gen.get_state().cpu(),
+                "noise_step": int(self._noise_step),
                 "spec": dict(extractor=self._extractor, pi=self.policy.spec["pi"], qf=self._critic_arch, horizon=self.H,
                              gamma=self.gamma, learning_rate=self.lr, algo=type(self).__name__,
                              share_features_extractor=bool(getattr(self, "_share_extractor", False)))}
@@ -379,6 +396,7 @@ class BPTT:
             self.exp_avg_sq.copy_(d["exp_avg_sq"])
             self._opt_step, self.num_timesteps = int(d["opt_step"]), int(d.get("num_timesteps", 0))
             self._gen.set_state(d["rng"])
+            self._noise_step = int(d.get("noise_step", 0))
 
     def save(self, path: str):
         if not self.reference_actor:

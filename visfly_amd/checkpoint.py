@@ -170,7 +170,7 @@ def _param_order(policy):
 def _hyper(trainer) -> dict:
     keys = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
             "lr", "weight_decay", "adam_eps", "betas", "normalize_advantage", "target_kl", "seed", "H", "num_timesteps", "_opt_step",
-            "clip_range_vf")
+            "clip_range_vf", "_noise_step")
     out = {k: getattr(trainer, k) for k in keys if hasattr(trainer, k)}
     # schedules (callables of progress_remaining) are archived as their current value: an archive holds data, not code
     out = {k: (trainer._now(v) if callable(v) else v) for k, v in out.items()}
@@ -270,4 +270,6 @@ def load_into(trainer, path: str, load_optimizer: bool = True):
                           f"({len(st)} vs {len(order)} tensors) -- Adam moments NOT restored", stacklevel=2)
     if isinstance(data, dict) and "num_timesteps" in data and not isinstance(data["num_timesteps"], dict):
         trainer.num_timesteps = int(data["num_timesteps"])
+    if isinstance(data, dict) and hasattr(trainer, "_noise_step") and isinstance(data.get("_noise_step"), int):
+        trainer._noise_step = data["_noise_step"]     # BPTT / SHAC over a globally keyed env: rows of vf_noise_fill drawn so far
     return trainer

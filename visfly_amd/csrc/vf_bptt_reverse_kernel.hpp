@@ -216,8 +216,8 @@ extern template struct BpttReverseSet<NetSacNav, false>;
 namespace vf {
 
 // layout stamp of what a BPTT plugin's reverse sweep is handed (vf_chain_plugin.hpp: ChainPlugin::bptt_rev_abi)
-constexpr unsigned kBpttRevPluginAbi = 0x42560002u ^ (unsigned)(sizeof(BwdArgsChain) * 31u + sizeof(RevArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
-                                                               sizeof(vf_env_cfg) * 5u);
+constexpr unsigned kBpttRevPluginAbi = 0x42560003u ^ (unsigned)(sizeof(BwdArgsChain) * 31u + sizeof(RevArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
+                                                               sizeof(vf_env_dev) * 5u);
 
 }  // namespace vf
 

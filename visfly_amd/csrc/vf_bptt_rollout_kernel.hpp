@@ -266,8 +266,8 @@ extern template struct BpttRolloutSet<NetSacNav, false>;
 namespace vf {
 
 // layout stamp of what a BPTT plugin's roll-out is handed (vf_chain_plugin.hpp: ChainPlugin::bptt_roll_abi)
-constexpr unsigned kBpttRollPluginAbi = 0x42520001u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(RollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
-                                                                sizeof(vf_env_cfg) * 5u + sizeof(ChainArgs) * 3u);
+constexpr unsigned kBpttRollPluginAbi = 0x42520002u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(RollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
+                                                                sizeof(vf_env_dev) * 5u + sizeof(ChainArgs) * 3u);
 
 }  // namespace vf
 

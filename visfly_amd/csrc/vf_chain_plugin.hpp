@@ -16,7 +16,8 @@
 namespace vf {
 
 // layout stamp: both sides are compiled from the same headers; a plugin built against other struct layouts is refused
-constexpr unsigned kChainPluginAbi = 0x56460004u ^ (unsigned)(sizeof(vf_mlp_desc) * 31u + sizeof(vf_mlp_bwd_desc) * 17u + sizeof(ChainArgs) * 7u +
+// (0005: the env constant block the persistent launches are handed is a vf_env_dev -- vf_env_cfg + the first global agent id)
+constexpr unsigned kChainPluginAbi = 0x56460005u ^ (unsigned)(sizeof(vf_mlp_desc) * 31u + sizeof(vf_mlp_bwd_desc) * 17u + sizeof(ChainArgs) * 7u +
                                                             sizeof(BwdArgsChain) * 5u + sizeof(PpoRowArgs) * 3u + sizeof(ReparamFwd) + sizeof(ReparamBwd));
 
 // out1 == null: the policy-only class (no value trunk).  M_choice > 0: the rows-per-wave choice is made for M_choice rows

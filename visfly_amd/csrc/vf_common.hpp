@@ -54,7 +54,19 @@ inline bool use_split(int agents_padded, const vf_dyn_cfg& cfg)
     return agents_padded <= 32768;   // measured on MI355X: 32768 agents 9.4 us (split) vs 11.3 us; 65536: 13.3 vs 12.5
 }
 
+// Device constant block of an env handle (vf_env::d_cfg): the public vf_env_cfg, whose layout the ABI freezes, followed by what a
+// handle carries beyond it.  The kernels keep their `const vf_env_cfg*` argument (the block's first member); env_agent0 reads the tail.
+struct vf_env_dev {
+    vf_env_cfg cfg;
+    unsigned agent0;   // global id of the handle's first agent (vf_env_set_agent_offset): the Philox counter word of row i is agent0 + i
+    unsigned pad;
+};
+
 #ifdef __HIPCC__
+// `e` must be the handle's device block (what the step / roll-out kernels get through their pointer argument), NOT a by-value copy
+// of a vf_env_cfg: k_env_reset takes the value in its argument struct instead
+__device__ __forceinline__ unsigned env_agent0(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_dev&>(e).agent0; }
+
 // ---- Philox4x32-10 counter RNG (on-device spawner, exploration noise of the policy head) ----
 struct U4 {
     unsigned x, y, z, w;
@@ -74,6 +86,21 @@ __device__ __forceinline__ U4 philox4x32_10(U4 ctr, unsigned k0, unsigned k1)
 }
 
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x & 0xFFFFFFu) * (1.0f / 16777216.0f); }
+
+// Domain tags (fourth counter word) of the per-row normal streams: the PPO head's exploration noise and the noise rows of the
+// BPTT / SHAC trainers (vf_noise_fill) never share a Philox block, whatever their keys and steps
+constexpr unsigned kTagPpoNoise = 0xac7u, kTagRowNoise = 0xb977u;
+
+// four standard normals of ONE Philox block with counter {row, step lo, step hi, tag}: two Box-Muller pairs (u1, u3 in (0, 1])
+__device__ __forceinline__ void philox_normal4(unsigned row, unsigned long long step, unsigned tag, unsigned long long seed, float* e)
+{
+    const U4 r = philox4x32_10(U4{row, (unsigned)step, (unsigned)(step >> 32), tag}, (unsigned)seed, (unsigned)(seed >> 32));
+    const float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f), u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
+    const float u3 = ((float)(r.z >> 8) + 1.0f) * (1.0f / 16777216.0f), u4 = (float)(r.w >> 8) * (1.0f / 16777216.0f);
+    const float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
+    const float two_pi = 6.28318530717958647692f;
+    e[0] = ra * cosf(two_pi * u2); e[1] = ra * sinf(two_pi * u2); e[2] = rb * cosf(two_pi * u4); e[3] = rb * sinf(two_pi * u4);
+}
 
 // ---- activations of the MLP layers (vf_mlp_layer.relu / vf_mlp_bwd_layer.act: VF_ACTIVATION_*) ----
 // create_mlp's `activation_fn` (utils/policies/extractors.py:376-449; the aliases of policies.py:64-69): ReLU, Tanh, ELU (alpha = 1),

@@ -228,6 +228,7 @@ struct EnvResetArgs {
     int k, g_race;
     const int* idx;
     const float* fs;  // (k,22) or null
+    unsigned agent0;  // vf_env::agent0 (the cfg arrives by value here: no vf_env_dev tail to read it from)
 };
 
 template <int KIND>
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const 
         for (int d = 0; d < 4; ++d) { s.wm[d] = f[13 + d]; s.T[d] = f[17 + d]; }
         s.t = f[21];
     } else {
-        spawn_agent(e, i, episode, r.idx != nullptr, s);
+        spawn_agent(e, r.agent0, i, episode, r.idx != nullptr, s);
     }
     for (int q = 0; q < c.delay_steps; ++q) *granule(r.d.S, r.d.G, i, VF_G_RING + q) = make_float4(0.f, 0.f, 0.f, 0.f);
     const Collision col = bbox_collision(e, s.p);
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const 
     if (r.d.g_drag >= 0) {
         if (e.drag_random > 0.0f && !(r.fs && !pad)) {  // device spawn: per-agent drag factors
             float4 kl4, kq4;
-            spawn_drag(c, e, i, episode, kl4, kq4);
+            spawn_drag(c, e, r.agent0, i, episode, kl4, kq4);
             *granule(r.d.S, r.d.G, i, r.d.g_drag) = kl4;
             *granule(r.d.S, r.d.G, i, r.d.g_drag + 1) = kq4;
         } else if (!r.idx) {  // mean coefficients; a host-side (replay) randomisation overwrites them
@@ -284,6 +285,16 @@ __global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const 
         race.z = __int_as_float(0);
         *granule(r.d.S, r.d.G, i, r.g_race) = race;
     }
+}
+
+// vf_env_set_agent_offset on a bound slab: the prefetched re-spawn copies were drawn for the old ids and their episode tags would still
+// match.  Tag 0 is an episode nobody starts (the first one is 1)
+__global__ __launch_bounds__(kBlock) void k_spawn_tags_clear(float* S, int G, int Npad, int g_spawn)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= Npad) return;
+    granule(S, G, i, g_spawn)->x = 0.0f;
+    granule(S, G, i, g_spawn + 4)->x = 0.0f;
 }
 
 __global__ __launch_bounds__(kBlock) void k_env_query(const vf_dyn_cfg c, const vf_env_cfg e, const DynArgs d, int g_race,
@@ -517,7 +528,7 @@ int vf_env_create(const vf_dyn_cfg* dyn, const vf_env_cfg* env, int32_t N, int32
     h->g_race = racing ? h->dyn.g_extra : -1;
     h->g_spawn = env->spawn_prefetch ? h->dyn.g_extra + racing : -1;
     int rc = vf::upload_cfg(h->dyn.cfg, &h->dyn.d_cfg);
-    if (rc == VF_OK) rc = vf::upload_cfg(h->cfg, &h->d_cfg);
+    if (rc == VF_OK) rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg);
     if (rc == VF_OK && h->g_spawn >= 0 &&
         hipMalloc(reinterpret_cast<void**>(&h->d_stale), (size_t)2 * (h->dyn.Npad / 64) * sizeof(unsigned long long)) != hipSuccess) {
         h->d_stale = nullptr;            // no bits: the helper compares every tag, as before
@@ -543,6 +554,29 @@ void vf_env_destroy(vf_env* h)
 
 int32_t vf_env_granules(const vf_env* h) { return h ? h->dyn.G : 0; }
 
+int vf_env_set_agent_offset(vf_env* h, int64_t first_agent)
+{
+    if (!h) return vf::fail(VF_EINVAL, "vf_env_set_agent_offset: null handle");
+    if (first_agent < 0 || first_agent + (int64_t)h->dyn.N > (int64_t)1 << 32)
+        return vf::fail(VF_EINVAL, "vf_env_set_agent_offset: agents [%lld, %lld) do not fit the 32-bit counter word", (long long)first_agent,
+                        (long long)first_agent + h->dyn.N);
+    // hipMemcpy from pageable memory returns after the copy and is ordered behind the null stream's work only: a launch of this
+    // handle still in flight on another stream must not see the block change under it
+    VF_HIP(hipDeviceSynchronize());
+    if (int rc = vf::upload_env_dev(h->cfg, (unsigned)first_agent, &h->d_cfg)) return rc;
+    h->agent0 = (unsigned)first_agent;
+    if (h->dyn.S && h->g_spawn >= 0) {
+        hipLaunchKernelGGL(vf::k_spawn_tags_clear, dim3(h->dyn.Npad / vf::kBlock), dim3(vf::kBlock), 0, nullptr, h->dyn.S, h->dyn.G, h->dyn.Npad,
+                           h->g_spawn);
+        VF_HIP(hipGetLastError());
+        VF_HIP(hipDeviceSynchronize());
+    }
+    h->stale_all = 1;
+    return VF_OK;
+}
+
+int64_t vf_env_agent_offset(const vf_env* h) { return h ? (int64_t)h->agent0 : -1; }
+
 int64_t vf_env_slab_floats(const vf_env* h) { return h ? (int64_t)h->dyn.Npad * h->dyn.G * 4 : 0; }
 
 int vf_env_bind(vf_env* h, float* slab)
@@ -563,7 +597,7 @@ int vf_env_reset(vf_env* h, const int32_t* idx, int32_t k, const float* full_sta
     h->stale_all = 1;            // episode counters / spawn copies change behind the stale bits' back
     if (!idx) h->dyn.tick = 0;   // full reset: head words go to 0 (k_env_reset) and so does the launch-uniform phase
     if (!idx) h->dyn.vel_strided = 1;   // DroneEnvsBase.reset always passes the randomizer's velocities (droneEnv.py:282)
-    vf::EnvResetArgs r{dyn_args(h, nullptr, nullptr), n, h->g_race, idx, full_state};
+    vf::EnvResetArgs r{dyn_args(h, nullptr, nullptr), n, h->g_race, idx, full_state, h->agent0};
     hipStream_t st = vf::as_stream(stream);
     const dim3 grid(vf::blocks_for(n)), block(vf::kBlock);
     switch (h->cfg.kind) {

@@ -89,7 +89,7 @@ extern "C" int vf_dyn_step_bwd(vf_dyn* h, const float* tape_slab, const float* a
     if (!h->d_env_dummy) {
         vf_env_cfg z{};
         z.kind = VF_ENV_HOVER;
-        if (int rc = vf::upload_cfg(z, &h->d_env_dummy)) return rc;
+        if (int rc = vf::upload_env_dev(z, 0u, &h->d_env_dummy)) return rc;
     }
     const size_t lds = (size_t)S * vf::kSave * vf::kBlock * sizeof(float);
     BwdKernel k = pick_bwd<VF_ENV_HOVER>(h->cfg);

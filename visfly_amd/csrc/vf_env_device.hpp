@@ -236,16 +236,18 @@ __device__ __forceinline__ void sincos_spawn(float x, float& sn, float& cs)
 // UniformStateRandomizer._generate + safe_generate (utils/randomization.py:64-96,153-170) and
 // UnionRandomizer (:284-296) for one agent.  Draw order per agent mirrors the reference
 // (pos, ori, vel, ang-vel, then the union pick and t); the stream itself is Philox keyed by
-// (seed, agent, episode) instead of the reference's global MT19937, so spawns are statistically
+// (seed, agent0 + agent, episode) -- agent0: the global id of the handle's first row, 0 unless vf_env_set_agent_offset moved it, so
+// a shard of a larger population draws what the whole population's rows draw -- instead of the reference's global MT19937, so spawns are statistically
 // -- not bitwise -- equivalent; bitwise parity uses host-replayed states (vf_env_reset).
 // Three Philox blocks per spawn: the twelve uniforms take the low 24 bits of the twelve words, the union pick and the
 // indexed reset's t take the twelve spare top bytes (Philox output bits are independent; a fourth block was 90 instructions).
-__device__ __forceinline__ void spawn_agent(const vf_env_cfg& e, int agent, unsigned episode, bool indexed, Agent& s)
+__device__ __forceinline__ void spawn_agent(const vf_env_cfg& e, unsigned agent0, int agent, unsigned episode, bool indexed, Agent& s)
 {
     const unsigned k0 = (unsigned)e.seed, k1 = (unsigned)(e.seed >> 32);
-    const U4 r0 = philox4x32_10(U4{(unsigned)agent, episode, 0u, 0x5eedu}, k0, k1);
-    const U4 r1 = philox4x32_10(U4{(unsigned)agent, episode, 1u, 0x5eedu}, k0, k1);
-    const U4 r2 = philox4x32_10(U4{(unsigned)agent, episode, 2u, 0x5eedu}, k0, k1);
+    const unsigned id = agent0 + (unsigned)agent;
+    const U4 r0 = philox4x32_10(U4{id, episode, 0u, 0x5eedu}, k0, k1);
+    const U4 r1 = philox4x32_10(U4{id, episode, 1u, 0x5eedu}, k0, k1);
+    const U4 r2 = philox4x32_10(U4{id, episode, 2u, 0x5eedu}, k0, k1);
     const float u[12] = {u01(r0.x), u01(r0.y), u01(r0.z), u01(r0.w), u01(r1.x), u01(r1.y),
                          u01(r1.z), u01(r1.w), u01(r2.x), u01(r2.y), u01(r2.z), u01(r2.w)};
     const unsigned pick = (r0.x >> 24) | ((r0.y >> 24) << 8) | ((r0.z >> 24) << 16) | ((r0.w >> 24) << 24);
@@ -275,12 +277,13 @@ __device__ __forceinline__ void spawn_agent(const vf_env_cfg& e, int agent, unsi
 
 // Drag domain randomisation (dynamics.py:244-246): k = k_mean * (clamp((U - .5) * 2 r, -.5, .5) + 1),
 // one factor per axis and per coefficient set, drawn per agent at every (re)spawn.
-__device__ __forceinline__ void spawn_drag(const vf_dyn_cfg& c, const vf_env_cfg& e, int agent, unsigned episode,
+__device__ __forceinline__ void spawn_drag(const vf_dyn_cfg& c, const vf_env_cfg& e, unsigned agent0, int agent, unsigned episode,
                                            float4& kl, float4& kq)
 {
     const unsigned k0 = (unsigned)e.seed, k1 = (unsigned)(e.seed >> 32);
-    const U4 a = philox4x32_10(U4{(unsigned)agent, episode, 4u, 0x5eedu}, k0, k1);
-    const U4 b = philox4x32_10(U4{(unsigned)agent, episode, 5u, 0x5eedu}, k0, k1);
+    const unsigned id = agent0 + (unsigned)agent;
+    const U4 a = philox4x32_10(U4{id, episode, 4u, 0x5eedu}, k0, k1);
+    const U4 b = philox4x32_10(U4{id, episode, 5u, 0x5eedu}, k0, k1);
     const float r2 = 2.0f * e.drag_random;
     const float ul[3] = {u01(a.x), u01(a.y), u01(a.z)}, uq[3] = {u01(b.x), u01(b.y), u01(b.z)};
     float fl[3], fq[3];

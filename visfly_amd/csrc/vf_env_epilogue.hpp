@@ -89,7 +89,7 @@ __device__ __forceinline__ void spawn_helper(const vf_env_cfg& e, const EnvArgs&
     float4* dst = granule(g.d.S, g.d.G, i, g.g_spawn_wr);
     if (__float_as_uint(dst->x) != need) {
         Agent s;
-        spawn_agent(e, i, need, true, s);
+        spawn_agent(e, env_agent0(e), i, need, true, s);
         const int gs = 64;                                   // float4 between two granules of one agent (wave-tile AoSoA)
         dst[0] = make_float4(__uint_as_float(need), s.p[0], s.p[1], s.p[2]);
         dst[gs] = make_float4(s.q.w, s.q.x, s.q.y, s.q.z);
@@ -270,14 +270,14 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
             s.v[0] = slot.g2.y; s.v[1] = slot.g2.z; s.v[2] = slot.g2.w;
             s.w[0] = slot.g3.y; s.w[1] = slot.g3.z; s.w[2] = slot.g3.w;
         } else {
-            spawn_agent(e, i, episode, true, s);
+            spawn_agent(e, env_agent0(e), i, episode, true, s);
         }
         reset_rotors(c, s);
         for (int q = 0; q < c.delay_steps; ++q)
             *granule(g.d.S, g.d.G, i, VF_G_RING + q) = make_float4(0.f, 0.f, 0.f, 0.f);     // dynamics.py:262-263
         if (g.d.g_drag >= 0 && e.drag_random > 0.0f) {
             float4 kl4, kq4;
-            spawn_drag(c, e, i, episode, kl4, kq4);
+            spawn_drag(c, e, env_agent0(e), i, episode, kl4, kq4);
             *granule(g.d.S, g.d.G, i, g.d.g_drag) = kl4;
             *granule(g.d.S, g.d.G, i, g.d.g_drag + 1) = kq4;
         }

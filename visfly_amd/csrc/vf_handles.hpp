@@ -38,7 +38,11 @@ struct vf_env {
     // next helper pass (after a reset, or after launches that re-spawn agents without maintaining the bits)
     unsigned long long* d_stale = nullptr;
     int stale_all = 1;
-    vf_env_cfg* d_cfg = nullptr;   // device copy of cfg, see vf_dyn::d_cfg
+    // device constant block, see vf_dyn::d_cfg: the first member of a vf_env_dev {cfg, agent0} (vf_common.hpp; upload_env_dev)
+    vf_env_cfg* d_cfg = nullptr;
+    // global id of row 0 (vf_env_set_agent_offset): every Philox counter keyed by agent uses agent0 + row, so a contiguous shard of a
+    // population draws exactly what those rows of the whole population draw.  0: rows are their own ids
+    unsigned agent0 = 0;
 };
 
 namespace vf {
@@ -76,6 +80,14 @@ inline int upload_cfg(const T& host, T** dev)
 {
     VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(T)));
     VF_HIP(hipMemcpy(*dev, &host, sizeof(T), hipMemcpyHostToDevice));
+    return VF_OK;
+}
+// an env handle's block: cfg + agent0 (allocated on first use, rewritten in place afterwards: the kernels keep the address)
+inline int upload_env_dev(const vf_env_cfg& cfg, unsigned agent0, vf_env_cfg** dev)
+{
+    const vf_env_dev host{cfg, agent0, 0u};
+    if (!*dev) VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(vf_env_dev)));
+    VF_HIP(hipMemcpy(*dev, &host, sizeof(vf_env_dev), hipMemcpyHostToDevice));
     return VF_OK;
 }
 template <class T>

@@ -1064,13 +1064,30 @@ __global__ __launch_bounds__(kBlock) void k_fold_partials(const float* __restric
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_head_sample(const float4* __restrict__ mean, const float* __restrict__ log_std,
                                                         float4* __restrict__ action, float* __restrict__ logp, int M,
-                                                        unsigned long long seed, unsigned long long step, int deterministic)
+                                                        unsigned row0, unsigned long long seed, unsigned long long step, int deterministic)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= M) return;
     float4 a;
-    logp[i] = head_sample_row(mean[i], log_std, i, seed, step, deterministic, a);
+    logp[i] = head_sample_row(mean[i], log_std, row0 + (unsigned)i, seed, step, deterministic, a);
     action[i] = a;
+}
+
+// vf_noise_fill: eps[t][i] = the four normals of the Philox block {row0 + i, step0 + t, kTagRowNoise}.  One thread per (t, agent), rows
+// coalesced: a wave stores 1 KiB contiguous per instruction.  Pure streaming write (non-temporal: nobody re-reads it from this launch)
+__global__ __launch_bounds__(kBlock) void k_noise_fill(float4* __restrict__ eps, int N, unsigned row0, unsigned long long seed,
+                                                       unsigned long long step0)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const unsigned t = blockIdx.y;
+    float e[4];
+    philox_normal4(row0 + (unsigned)i, step0 + t, kTagRowNoise, seed, e);
+    float4* dst = eps + (size_t)t * N + i;
+    __builtin_nontemporal_store(e[0], &dst->x);
+    __builtin_nontemporal_store(e[1], &dst->y);
+    __builtin_nontemporal_store(e[2], &dst->z);
+    __builtin_nontemporal_store(e[3], &dst->w);
 }
 
 // PPO clipped surrogate + value MSE + "entropy" (= mean log-prob for the squashed head), PPO.py:210-263
@@ -1853,13 +1870,30 @@ int vf_episode_stats(const uint8_t* done, const float* ep_return, const int32_t*
     return VF_OK;
 }
 
+int vf_head_sample_at(const float* mean, const float* log_std, float* action, float* log_prob, int32_t M, uint64_t row0, uint64_t seed,
+                      uint64_t step, int32_t deterministic, vf_stream_t stream)
+{
+    if (!mean || !log_std || !action || !log_prob || M <= 0) return vf::fail(VF_EINVAL, "vf_head_sample: bad argument");
+    if (row0 + (uint64_t)M > (uint64_t)1 << 32) return vf::fail(VF_EINVAL, "vf_head_sample_at: rows [row0, row0 + M) do not fit the 32-bit counter word");
+    hipLaunchKernelGGL(vf::k_head_sample, dim3(vf::blocks_for(M)), dim3(vf::kBlock), 0, vf::as_stream(stream),
+                       reinterpret_cast<const float4*>(mean), log_std, reinterpret_cast<float4*>(action), log_prob, M, (unsigned)row0,
+                       (unsigned long long)seed, (unsigned long long)step, deterministic);
+    VF_HIP(hipGetLastError());
+    return VF_OK;
+}
+
 int vf_head_sample(const float* mean, const float* log_std, float* action, float* log_prob, int32_t M, uint64_t seed,
                    uint64_t step, int32_t deterministic, vf_stream_t stream)
 {
-    if (!mean || !log_std || !action || !log_prob || M <= 0) return vf::fail(VF_EINVAL, "vf_head_sample: bad argument");
-    hipLaunchKernelGGL(vf::k_head_sample, dim3(vf::blocks_for(M)), dim3(vf::kBlock), 0, vf::as_stream(stream),
-                       reinterpret_cast<const float4*>(mean), log_std, reinterpret_cast<float4*>(action), log_prob, M,
-                       (unsigned long long)seed, (unsigned long long)step, deterministic);
+    return vf_head_sample_at(mean, log_std, action, log_prob, M, 0, seed, step, deterministic, stream);
+}
+
+int vf_noise_fill(float* eps, int32_t T, int32_t N, uint64_t row0, uint64_t seed, uint64_t step0, vf_stream_t stream)
+{
+    if (!eps || T <= 0 || N <= 0 || T > 65535) return vf::fail(VF_EINVAL, "vf_noise_fill: null output, T outside [1, 65535] or N <= 0");
+    if (row0 + (uint64_t)N > (uint64_t)1 << 32) return vf::fail(VF_EINVAL, "vf_noise_fill: rows [row0, row0 + N) do not fit the 32-bit counter word");
+    hipLaunchKernelGGL(vf::k_noise_fill, dim3(vf::blocks_for(N), T), dim3(vf::kBlock), 0, vf::as_stream(stream),
+                       reinterpret_cast<float4*>(eps), N, (unsigned)row0, (unsigned long long)seed, (unsigned long long)step0);
     VF_HIP(hipGetLastError());
     return VF_OK;
 }

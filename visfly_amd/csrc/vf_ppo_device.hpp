@@ -30,10 +30,11 @@ __device__ __forceinline__ float squashed_log_prob(const float* mu, const float*
     return lp;
 }
 
-// Squashed diagonal Gaussian head for row i (policies.py:177-181, SB3 SquashedDiagGaussianDistribution): action = tanh(mean +
+// Squashed diagonal Gaussian head for the row whose counter word is `row` (the row's index, plus the first global agent id where
+// the caller keys by global agent: vf_head_sample_at, vf_env_set_agent_offset) (policies.py:177-181, SB3 SquashedDiagGaussianDistribution): action = tanh(mean +
 // exp(log_std) eps), eps = Box-Muller over Philox(row, step; seed); -> log-prob of the action.  k_head_sample (vf_ppo.hip) and
 // the persistent PPO roll-out (vf_bptt_rollout.hip) share it.
-__device__ __forceinline__ float head_sample_row(const float4 m4, const float* __restrict__ log_std, int i, unsigned long long seed,
+__device__ __forceinline__ float head_sample_row(const float4 m4, const float* __restrict__ log_std, unsigned row, unsigned long long seed,
                                                  unsigned long long step, int deterministic, float4& action)
 {
     const float mu[4] = {m4.x, m4.y, m4.z, m4.w};
@@ -43,13 +44,8 @@ __device__ __forceinline__ float head_sample_row(const float4 m4, const float* _
 #pragma unroll
         for (int d = 0; d < 4; ++d) a[d] = tanhf(mu[d]);
     } else {
-        const U4 r = philox4x32_10(U4{(unsigned)i, (unsigned)step, (unsigned)(step >> 32), 0xac7u}, (unsigned)seed,
-                                   (unsigned)(seed >> 32));
-        const float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f), u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
-        const float u3 = ((float)(r.z >> 8) + 1.0f) * (1.0f / 16777216.0f), u4 = (float)(r.w >> 8) * (1.0f / 16777216.0f);
-        const float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
-        const float two_pi = 6.28318530717958647692f;
-        const float e[4] = {ra * cosf(two_pi * u2), ra * sinf(two_pi * u2), rb * cosf(two_pi * u4), rb * sinf(two_pi * u4)};
+        float e[4];
+        philox_normal4(row, step, kTagPpoNoise, seed, e);
 #pragma unroll
         for (int d = 0; d < 4; ++d) a[d] = tanhf(mu[d] + expf(ls[d]) * e[d]);
     }

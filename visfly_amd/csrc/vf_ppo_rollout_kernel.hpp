@@ -22,7 +22,7 @@ struct PpoRollArgs {
     float* obs_slots;               // [T][N][13] = RolloutBuffer.obs["state"] (RacingEnv2: 16 wide, like obs_final / rows0 / the terminal rows)
     float* obs_final;               // (N,13)
     const float* log_std;
-    unsigned long long noise_key, sample_step;      // step t samples with Philox counter sample_step + 1 + t (k_head_sample)
+    unsigned long long noise_key, sample_step;      // step t samples with Philox counter sample_step + 1 + t (k_head_sample), row word = the handle's agent0 + i
     // deferred TimeLimit bootstrap list + per-agent episode statistics (k_rollout_post_collect)
     const float* obs1;              // (N,w1) constant "target" rows or null
     int w1, capacity;
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
         mean.x = __shfl(mean.x, m); mean.y = __shfl(mean.y, m); mean.z = __shfl(mean.z, m); mean.w = __shfl(mean.w, m);
         VF_PT(0);
         float4 act;
-        const float lp = head_sample_row(mean, r.log_std, i, r.noise_key, r.sample_step + 1ull + (unsigned long long)t, 0, act);
+        const float lp = head_sample_row(mean, r.log_std, env_agent0(e) + (unsigned)i, r.noise_key, r.sample_step + 1ull + (unsigned long long)t, 0, act);
         r.actions[row] = act;
         r.log_probs[row] = lp;
         // ---- env step (k_env_rollout's body; ring_exchange with the action already in registers) ----
@@ -197,8 +197,8 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
 namespace vf {
 
 // layout stamp of what a roll-out plugin is handed (vf_chain_plugin.hpp: ChainPlugin::rollout_abi)
-constexpr unsigned kRolloutPluginAbi = 0x52300001u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(PpoRollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
-                                                               sizeof(vf_env_cfg) * 5u + sizeof(ChainArgs) * 3u);
+constexpr unsigned kRolloutPluginAbi = 0x52300002u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(PpoRollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
+                                                               sizeof(vf_env_dev) * 5u + sizeof(ChainArgs) * 3u);
 
 }  // namespace vf
 

@@ -237,13 +237,19 @@ class DroneGymEnvsBase:
             out_buffers: int = 0,
             spawn_prefetch: Optional[bool] = None,
             replay_trig: str = "torch",
+            agent_offset: Optional[int] = None,
     ):
         """out_buffers = R > 0: step() writes into a ring of R pre-allocated (obs, reward, done) sets instead of fresh tensors
         -- no allocation and no Python object construction on the hot path; what step t returned stays valid until step
         t + R.  0 (default) returns fresh tensors every step like the reference.
         spawn_prefetch (default: on for spawn="device" without requires_grad): the state an agent re-spawns into is drawn ahead of
         its episode end by helper blocks of the step launch and kept in the slab (8 granules per agent; include/visfly_amd.h
-        "Prefetched re-spawn") -- bit-identical results, the re-spawning wave no longer holds up the launch."""
+        "Prefetched re-spawn") -- bit-identical results, the re-spawning wave no longer holds up the launch.
+        agent_offset = global id of this env's first agent (an int, 0 included) marks the env as GLOBALLY KEYED: every device random
+        stream keyed by agent (spawns, drag randomisation, and the exploration noise of the trainers over this env) uses
+        agent_offset + row, so a contiguous shard of a population reproduces the matching rows of one env over the whole population
+        with the same seed (visfly_amd.parallel.shard_kwargs).  None (default): rows are their own ids and the trainers keep their
+        per-rank streams.  spawn="replay" has one global host stream and no per-agent key: an int is refused there."""
         if visual:
             raise NotImplementedError("visual=True needs the external Habitat-sim renderer; the MI355X engine "
                                       "covers the visual=False path (SURVEY.md 8)")
@@ -251,6 +257,15 @@ class DroneGymEnvsBase:
             raise ValueError("spawn must be 'device' or 'replay'")
         if replay_trig not in ("torch", "cr"):
             raise ValueError("replay_trig must be 'torch' or 'cr'")
+        if agent_offset is not None:
+            if isinstance(agent_offset, bool) or not isinstance(agent_offset, (int, np.integer)):
+                raise ValueError("agent_offset must be an int or None")
+            if spawn == "replay":
+                raise ValueError("agent_offset needs spawn='device': the replayed host stream (one global MT19937) has no per-agent key")
+            if agent_offset < 0 or agent_offset + num_agent_per_scene * num_scene > 2 ** 32:
+                raise ValueError(f"agents [{agent_offset}, {agent_offset + num_agent_per_scene * num_scene}) do not fit the 32-bit "
+                                 "counter word of the device streams")
+        self.agent_offset = None if agent_offset is None else int(agent_offset)
         self.device = th.device(device)
         if self.device.type != "cuda":
             raise VisflyError(f"visfly_amd envs run on an MI355X only (device='{device}'); there is no CPU fallback")
@@ -318,6 +333,8 @@ class DroneGymEnvsBase:
             h = _lib._vp()
             _lib.check(L.vf_env_create(self._dcfg, self._ecfg, N, 1 if drag_random else 0, h))
             self._h = h
+            if self.agent_offset is not None:
+                _lib.check(L.vf_env_set_agent_offset(h, self.agent_offset))
             G = int(L.vf_env_granules(h))
             floats = int(L.vf_env_slab_floats(h))
             self._slab = th.zeros((floats // (G * TILE * 4), G, TILE, 4), dtype=th.float32, device=self.device)

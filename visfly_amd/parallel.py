@@ -49,6 +49,20 @@ def shard(n_total: int, rank: int, world: int) -> Tuple[int, int]:
     return first, count
 
 
+def shard_kwargs(n_total: int, rank: int = None, world: int = None) -> dict:
+    """Env constructor keywords of this rank's shard of an `n_total`-agent population, globally keyed:
+    ``Env(**parallel.shard_kwargs(N), seed=S, ...)`` with the SAME seed on every rank draws, row for row, what one env of N agents
+    with ``agent_offset=0`` draws (envs/base.py: agent_offset).  rank / world default to the process group's."""
+    rank = globals()["rank"]() if rank is None else rank
+    world = world_size() if world is None else world
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} outside [0, {world})")
+    first, count = shard(n_total, rank, world)
+    if count <= 0:
+        raise ValueError(f"{n_total} agents over {world} ranks leave rank {rank} without one")
+    return dict(num_agent_per_scene=count, agent_offset=first)
+
+
 _native = {"comm": None, "tried": False}
 
 

@@ -962,6 +962,12 @@ class PPO:
         parallel.broadcast_(self.policy.flat)
         self.policy.mark_updated()
         self._noise_key = (int(seed) ^ (self.rank << 32)) & (2 ** 64 - 1)
+        # ... unless the env is globally keyed (envs/base.py: agent_offset): then the counter row of agent i is agent_offset + i on
+        # every rank and the key is the seed alone -- the shards' noise is the matching rows of ONE stream over the whole population
+        self._row0 = getattr(env, "agent_offset", None)
+        if self._row0 is not None:
+            self._noise_key = int(seed) & (2 ** 64 - 1)
+        self._row0 = self._row0 or 0
         self.buf = RolloutBuffer(n_steps, self.n_envs, obs_dims, self.device)
         n = self.policy.n_params
         dev = self.device
@@ -1043,9 +1049,9 @@ class PPO:
         action = th.empty((M, 4), device=self.device)
         logp = th.empty(M, device=self.device)
         self._sample_step += 1
-        _lib.check(_lib.lib().vf_head_sample(_ptr(mean), _ptr(self.policy.log_std), _ptr(action), _ptr(logp), M,
-                                             self._noise_key, self._sample_step, 1 if deterministic else 0,
-                                             self._stream()))
+        _lib.check(_lib.lib().vf_head_sample_at(_ptr(mean), _ptr(self.policy.log_std), _ptr(action), _ptr(logp), M, self._row0,
+                                                self._noise_key, self._sample_step, 1 if deterministic else 0,
+                                                self._stream()))
         return action, value.view(M), logp
 
     def predict_values(self, obs):
@@ -1087,8 +1093,8 @@ class PPO:
             action, logp = buf.actions[t], buf.log_probs[t]
             mean, _ = pol.forward({k: obs[k] for k in self.obs_keys}, save_activations=False, out_value=buf.values[t])
             self._sample_step += 1
-            _lib.check(L.vf_head_sample(_ptr(mean), _ptr(pol.log_std), _ptr(action), _ptr(logp), N, self._noise_key,
-                                        self._sample_step, 0, self._stream()))
+            _lib.check(L.vf_head_sample_at(_ptr(mean), _ptr(pol.log_std), _ptr(action), _ptr(logp), N, self._row0, self._noise_key,
+                                           self._sample_step, 0, self._stream()))
             for k in self.obs_keys:
                 buf.obs[k][t].copy_(obs[k])
             obs, reward, done, _info = env.step(action)

@@ -134,7 +134,7 @@ class SHAC(BPTT):
         b = self._buf = dict(obs={k: th.empty((H, N, pol.obs_dims[k]), **f) for k in keys}, action=th.empty((H, N, 4), **f),
                              reward=th.empty((H, N), **f), done=th.empty((H, N), **u8), ep_done=th.empty((H, N), **u8),
                              next_value=th.empty((H, N), **f))
-        eps = self._eps_override if self._eps_override is not None else th.randn((2 * H, N, 4), device=dev, generator=self._gen)
+        eps = self._eps_override if self._eps_override is not None else self._noise(2 * H, N)
         assert eps.shape == (2 * H, N, 4)
         eps_a = eps[0::2].contiguous()                                                 # [t] = noise of the action of step t
         drews, ls_rows = th.empty((H, N), **f), blk["value"]
@@ -217,6 +217,7 @@ class SHAC(BPTT):
             g_obs = d_in.get("state") if t > 0 else None
         if defer:
             pol.weight_grad_slots(N, H, d_mus, accumulate=True, d_value_all=d_lss)
+        self._horizon = dict(actions=b["action"], rewards=b["reward"], loss_vec=loss_vec)   # per-agent rows of the last horizon
         return loss_vec.mean() / self.world
 
     # ---- one iteration ------------------------------------------------------------------------------------------------------
@@ -304,7 +305,7 @@ class SHAC(BPTT):
         mu, ls = self.policy.forward({k: obs[k].detach().contiguous() for k in self.obs_keys}, save_activations=False, slot=self.H + 1)
         if deterministic:
             return th.tanh(mu), None
-        eps = th.randn((N, 4), device=self.device, generator=self._gen)
+        eps = self._noise(1, N)[0]
         action = th.empty((N, 4), device=self.device)
         self._head_fwd(mu, ls.contiguous(), eps, action)
         return action, None
