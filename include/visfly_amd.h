@@ -480,19 +480,25 @@ int vf_adv_normalize_segments(const float* adv, float* out, int32_t n_seg, int64
 #define VF_ACTIVATION_LEAKY_RELU 4
 
 /* Y[M][No] (+)= act(X[M][K] @ W^T + b)   nn.Linear + activation (extractors.py:421-445)
- *   W [No][K], b [No] or NULL; ldx / ldy row strides in floats; relu: VF_ACTIVATION_*; K, No <= 128. */
+ *   W [No][K], b [No] or NULL; ldx / ldy row strides in floats; relu: VF_ACTIVATION_*; K, No <= 512.
+ * Up to 128 x 128 a workgroup keeps the whole weight matrix in LDS (weight-stationary); a layer with K > 128 or No > 128 runs on
+ * kernels that stream both operands in reduction chunks (vf_linear_is_wide tells which; the same holds for the three gradient
+ * entry points below).  Columns >= No of a wider ldy are never written. */
 int vf_linear_fwd(const float* X, int32_t ldx, const float* W, const float* b, float* Y, int32_t ldy,
                   int32_t M, int32_t K, int32_t No, int32_t relu, vf_stream_t stream);
 
 /* dX[M][K] (+)= (dY * act'(Y)) @ W ; Ymask = the layer's saved post-activation output or NULL (no activation), act = its
- * VF_ACTIVATION_* (0 with a Ymask: ReLU); accumulate != 0 adds into dX (a tensor consumed by two branches). */
+ * VF_ACTIVATION_* (0 with a Ymask: ReLU); accumulate != 0 adds into dX (a tensor consumed by two branches).  K, No <= 512. */
 int vf_linear_bwd_data(const float* dY, int32_t lddy, const float* Ymask, int32_t ldym, const float* W,
                        float* dX, int32_t lddx, int32_t M, int32_t K, int32_t No, int32_t accumulate, int32_t act,
                        vf_stream_t stream);
 
 /* dW[No][K] = (dY * act'(Y))^T @ X, db[No] = column sums; deterministic two-stage reduction.
- * scratch: vf_linear_bwd_scratch_floats(M, K, No) floats. */
+ * scratch: vf_linear_bwd_scratch_floats(M, K, No) floats.  K, No <= 512. */
 int64_t vf_linear_bwd_scratch_floats(int32_t M, int32_t K, int32_t No);
+/* 1 if a K -> No layer is served by the streamed-operand kernels (K > 128 or No > 128), 0 if by the weight-stationary ones: the
+ * predicate the four vf_linear_* entry points dispatch on (pure host function, no device needed). */
+int vf_linear_is_wide(int32_t K, int32_t No);
 int vf_linear_bwd_weight(const float* dY, int32_t lddy, const float* Ymask, int32_t ldym, const float* X,
                          int32_t ldx, float* dW, float* db, int32_t M, int32_t K, int32_t No, float* scratch,
                          int32_t act, vf_stream_t stream);

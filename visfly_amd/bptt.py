@@ -126,7 +126,11 @@ class BPTT:
     def _make_reference_actor(self, obs, policy_kwargs, seed):
         """td_policies.Actor (:146-252): extractor -> (latent_pi -> mu | log_latent_pi -> log_std); nn.Linear default initialisation
         (SB3's SAC policies do not use orthogonal init), log_latent_pi = deepcopy(latent_pi) (:205).  One MlpPolicy layer table with
-        two 4-wide heads; sets self._extractor / _ext_keys / _critic_arch (SHAC builds its critics from them)."""
+        two 4-wide heads; sets self._extractor / _ext_keys / _critic_arch (SHAC builds its critics from them).
+        ``net_arch``: dict(pi=..., qf=...) or a plain list (SB3's get_actor_critic_arch: the same sizes for actor and critics).  Without
+        one the trunks are [64, 64] here; the REFERENCE's default is [256, 256] (MTDPolicy's net_arch=None, td_policies.py:295, which
+        SB3's SACPolicy turns into [256, 256]) -- ask for it with ``policy_kwargs=dict(net_arch=[256, 256])``.  Layers wider than 128 (up
+        to 512) run layer by layer on the wide linear kernels: no persistent horizon launches for such a network."""
         pk = dict(policy_kwargs or {})
         na = pk.get("net_arch")
         self._critic_arch = getattr(self, "_critic_arch", None)

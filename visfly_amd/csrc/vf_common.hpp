@@ -238,5 +238,15 @@ int mlp_wgrad_fold_blocks(const vf_mlp_bwd_desc* d);
 int mlp_wgrad_launch(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, double* sq_part,
                      const vf_stats_fold* loss_stats, hipStream_t st);
 int mlp_wgrad_launch_layers(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, unsigned layer_mask, hipStream_t st);
+// vf_linear_wide.hip: the streamed-operand kernels behind vf_linear_* for layers the weight-stationary kernels cannot hold.
+// The one predicate every entry point dispatches on (exported as vf_linear_is_wide): up to 128 x 128 the old kernels keep serving
+constexpr int kLinearNarrowMax = 128, kLinearWideMax = 512;
+inline bool linear_is_wide(int K, int No) { return K > kLinearNarrowMax || No > kLinearNarrowMax; }
+int linear_wide_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, int M, int K, int No, int act, hipStream_t st);
+int linear_wide_bwd_data(const float* dY, int lddy, const float* Ymask, int ldym, const float* W, float* dX, int lddx, int M, int K, int No,
+                         int accumulate, int act, hipStream_t st);
+int linear_wide_splits(int M, int K, int No);      // row ranges of M = partials of No*K + No floats the weight gradient writes
+int linear_wide_wgrad_partials(const float* dY, int lddy, const float* Ymask, int ldym, const float* X, int ldx, float* part, int M, int K,
+                               int No, int act, hipStream_t st);
 
 }  // namespace vf

@@ -1507,8 +1507,12 @@ int vf_adv_normalize_segments(const float* adv, float* out, int32_t n_seg, int64
 int vf_linear_fwd(const float* X, int32_t ldx, const float* W, const float* b, float* Y, int32_t ldy, int32_t M,
                   int32_t K, int32_t No, int32_t relu, vf_stream_t stream)
 {
-    if (!X || !W || !Y || M <= 0 || K <= 0 || No <= 0 || K > 128 || No > 128 || ldx < K || ldy < No)
-        return vf::fail(VF_EINVAL, "vf_linear_fwd: bad argument (K, No <= 128)");
+    if (!X || !W || !Y || M <= 0 || K <= 0 || No <= 0 || K > vf::kLinearWideMax || No > vf::kLinearWideMax || ldx < K || ldy < No)
+        return vf::fail(VF_EINVAL, "vf_linear_fwd: bad argument (K, No <= 512)");
+    if (vf::linear_is_wide(K, No)) {
+        if (relu < 0 || relu > VF_ACTIVATION_LEAKY_RELU) return vf::fail(VF_EINVAL, "vf_linear_fwd: activation kind %d", relu);
+        return vf::linear_wide_fwd(X, ldx, W, b, Y, ldy, M, K, No, relu, vf::as_stream(stream));
+    }
     const size_t lds = linear_lds_bytes(false, K, No);
     const dim3 grid(linear_grid(M)), block(vf::kBlock);
     hipStream_t st = vf::as_stream(stream);
@@ -1522,9 +1526,11 @@ int vf_linear_fwd(const float* X, int32_t ldx, const float* W, const float* b, f
 int vf_linear_bwd_data(const float* dY, int32_t lddy, const float* Ymask, int32_t ldym, const float* W, float* dX,
                        int32_t lddx, int32_t M, int32_t K, int32_t No, int32_t accumulate, int32_t act, vf_stream_t stream)
 {
-    if (!dY || !W || !dX || M <= 0 || K <= 0 || No <= 0 || K > 128 || No > 128 || lddy < No || lddx < K || act < 0 ||
-        act > VF_ACTIVATION_LEAKY_RELU)
-        return vf::fail(VF_EINVAL, "vf_linear_bwd_data: bad argument (K, No <= 128)");
+    if (!dY || !W || !dX || M <= 0 || K <= 0 || No <= 0 || K > vf::kLinearWideMax || No > vf::kLinearWideMax || lddy < No || lddx < K ||
+        act < 0 || act > VF_ACTIVATION_LEAKY_RELU)
+        return vf::fail(VF_EINVAL, "vf_linear_bwd_data: bad argument (K, No <= 512)");
+    if (vf::linear_is_wide(K, No))
+        return vf::linear_wide_bwd_data(dY, lddy, Ymask, ldym, W, dX, lddx, M, K, No, accumulate, act, vf::as_stream(stream));
     const size_t lds = linear_lds_bytes(true, K, No);
     if (int rc = allow_lds(vf::k_linear<true>, lds)) return rc;
     hipLaunchKernelGGL((vf::k_linear<true>), dim3(linear_grid(M)), dim3(vf::kBlock), lds,
@@ -1533,8 +1539,11 @@ int vf_linear_bwd_data(const float* dY, int32_t lddy, const float* Ymask, int32_
     return VF_OK;
 }
 
+int vf_linear_is_wide(int32_t K, int32_t No) { return vf::linear_is_wide(K, No) ? 1 : 0; }
+
 int64_t vf_linear_bwd_scratch_floats(int32_t M, int32_t K, int32_t No)
 {
+    if (vf::linear_is_wide(K, No)) return (int64_t)vf::linear_wide_splits(M, K, No) * ((int64_t)No * K + No);
     const int rpb = wgrad_rows_per_block(M);
     const int nblk = (M + rpb - 1) / rpb;
     return (int64_t)nblk * ((int64_t)No * K + No);
@@ -1544,8 +1553,18 @@ static int linear_bwd_weight(const float* dY, int32_t lddy, const float* Ymask, 
                              float* dW, float* db, int32_t M, int32_t K, int32_t No, float* scratch, vf_stream_t stream,
                              int accumulate, int act)
 {
-    if (!dY || !X || !dW || !scratch || M <= 0 || K <= 0 || No <= 0 || K > 128 || No > 128 || act < 0 || act > VF_ACTIVATION_LEAKY_RELU)
-        return vf::fail(VF_EINVAL, "vf_linear_bwd_weight: bad argument (K, No <= 128)");
+    if (!dY || !X || !dW || !scratch || M <= 0 || K <= 0 || No <= 0 || K > vf::kLinearWideMax || No > vf::kLinearWideMax || act < 0 ||
+        act > VF_ACTIVATION_LEAKY_RELU)
+        return vf::fail(VF_EINVAL, "vf_linear_bwd_weight: bad argument (K, No <= 512)");
+    if (vf::linear_is_wide(K, No)) {
+        hipStream_t st = vf::as_stream(stream);
+        if (int rc = vf::linear_wide_wgrad_partials(dY, lddy, Ymask, ldym, X, ldx, scratch, M, K, No, act, st)) return rc;
+        const int n = No * K + No;
+        hipLaunchKernelGGL(vf::k_fold_partials, dim3((n + 63) / 64), dim3(vf::kBlock), 0, st, scratch, vf::linear_wide_splits(M, K, No), n,
+                           No * K, No, dW, db, accumulate);
+        VF_HIP(hipGetLastError());
+        return VF_OK;
+    }
     const int rpb = wgrad_rows_per_block(M);
     const int nblk = (M + rpb - 1) / rpb;
     const int nt = (No + 31) >> 5, kt = (K + 31) >> 5;

@@ -35,6 +35,10 @@ _TORCH_ACT = {1: "ReLU", 2: "Tanh", 3: "ELU", 4: "LeakyReLU"}
 # weight_grad_slots: rows per weight-gradient launch of a horizon (profiles/r06_bptt_wgrad_chunks.txt)
 WGRAD_SPLIT_ROWS = 524288
 
+# widest layer (in or out) of an MlpPolicy: the per-layer kernels' limit (vf_linear_*: K, No <= 512) / of a network the one-launch,
+# register-chained and persistent kernels can run (K, No <= 128: vf_linear_is_wide)
+MAX_WIDTH, FUSED_MAX_WIDTH = 512, 128
+
 
 def activation_kind(a) -> int:
     """'relu' / 'Tanh' / nn.ELU / nn.LeakyReLU() ... -> VF_ACTIVATION_*"""
@@ -147,8 +151,8 @@ class MlpPolicy:
             off += d * d + d
         self.n_total = off
         for ly in self.layers:
-            if ly.K > 128 or ly.No > 128:
-                raise ValueError(f"layer widths up to 128 are supported by the MFMA linear kernels (layer {ly.src} -> {ly.dst} is {ly.K} -> {ly.No}"
+            if ly.K > MAX_WIDTH or ly.No > MAX_WIDTH:
+                raise ValueError(f"layer widths up to {MAX_WIDTH} are supported by the MFMA linear kernels (layer {ly.src} -> {ly.dst} is {ly.K} -> {ly.No}"
                                  + (f": the extractor outputs {feat_w - sum(self.obs_dims[k] for k in self.passthrough)} features (+) "
                                     f"{sum(self.obs_dims[k] for k in self.passthrough)} pass-through columns -- narrow the extractors' last layers"
                                     if self.passthrough and ly.K == feat_w else "") + ")")
@@ -177,7 +181,11 @@ class MlpPolicy:
         self._bufs: Dict[tuple, Dict[str, th.Tensor]] = {}
         self._gbufs: Dict[int, Dict[str, th.Tensor]] = {}
         self._scratch = None
-        self._plan = self._plan_fused()
+        # a layer wider than 128 in or out: only the per-layer entry points (vf_linear_*) have kernels for it -- operands streamed
+        # instead of a resident weight matrix (csrc/vf_linear_wide.hip); the one-launch kernels, the chain classes and the persistent
+        # horizons stop at 128, so such a network has no plan and runs layer by layer like one with too many buffers
+        self.wide = any(ly.K > FUSED_MAX_WIDTH or ly.No > FUSED_MAX_WIDTH for ly in self.layers)
+        self._plan = None if self.wide else self._plan_fused()
         self._descs = {}
         # chain kernels of a shape the library holds no instance of: compiled on first use (visfly_amd/_jit.py)
         # (heads (4, 1) with the log_std parameter: the PPO policies' actor-critic; (4, 4) without: the SAC-style Actor of BPTT / SHAC;
@@ -213,6 +221,12 @@ class MlpPolicy:
         if not getattr(self, "_warned_fallback", False):
             self._warned_fallback = True
             import warnings
+            if self.wide:
+                warnings.warn(f"visfly_amd: {what}: this network has layers wider than {FUSED_MAX_WIDTH} "
+                              f"(extractor {self.spec['extractor']}, pi {self.spec['pi']}, vf {self.spec['vf']}); they run layer by layer "
+                              "on the wide (streamed-operand) MFMA linear kernels -- no one-launch, register-chained or persistent path",
+                              stacklevel=3)
+                return
             warnings.warn(f"visfly_amd: {what} has no register-chained instance for this network "
                           f"(extractor {self.spec['extractor']}, pi {self.spec['pi']}, vf {self.spec['vf']}); "
                           "falling back to the block-tile MFMA kernels (about half the throughput)", stacklevel=3)
@@ -447,6 +461,8 @@ class MlpPolicy:
             if rc:
                 _lib.check(rc)
             return b["mean"], (vout if need_value else None)
+        if self.wide:
+            self._warn_fallback("forward")
         for ly in self.layers:
             X, Y = b[ly.src], b[ly.dst]
             rc = L.vf_linear_fwd(_ptr(X, ly.sc), X.shape[1], _ptr(self.flat, ly.w_off), _ptr(self.flat, ly.b_off),
