@@ -658,6 +658,27 @@ BPTT_CASES = {
                                         "orientation": {"mean": [0., 0., 0.], "half": [0.2, 0.2, 1.0]},
                                         "velocity": {"mean": [1., 0., 0.], "half": [1., .5, .5]}}]}}),
                   [-0.3, 0, 0, 0], 0.5, 12),
+    # ---- saturation / clamp cases (7th entry: options of gen_bptt).  layout: sat_actions; init: planted initial state ----
+    "bptt_racing_thrust_sat": ("racing", RACING_DYN, dict(max_episode_steps=1000), None, None, 12, dict(layout="thrust")),
+    "bptt_hover_thrust_sat_nodelay": ("hover", dict(RACING_DYN, ctrl_delay=False, comm_delay=0.0), dict(max_episode_steps=1000), None, None, 12,
+                                      dict(layout="thrust")),
+    "bptt_hover_thrust_sat_rk4": ("hover", dict(RACING_DYN, integrator="rk4"), dict(max_episode_steps=1000), None, None, 12, dict(layout="thrust")),
+    "bptt_hover_bodyrate_sat": ("hover", ENV_DYN, dict(max_episode_steps=1000), None, None, 12, dict(layout="full")),
+    # _ugly_fix masks (plant_state_clamps).  The ceiling side of p_z is dropped: p_z = 20 lies above the scene box (z <= 8,
+    # droneEnv.py:129), so the step that clips there is out of bounds and ends the episode -- its adjoint is cut, the mask is never
+    # seen live.  The same holds for x / y at +-100 (box +-30).  The floor is live only with is_collision_reset=False.
+    "bptt_hover_state_clamps": ("hover", ENV_DYN, dict(max_episode_steps=1000, is_collision_reset=False), [-1 / 3, 0, 0, 0], 0.3, 12,
+                                dict(init="state_clamps")),
+    # the benchmark's horizon, episodes of 20 steps so that re-spawns fall inside it; N = 16 keeps the file below the size cap
+    "bptt_racing_thrust_h64": ("racing", RACING_DYN, dict(max_episode_steps=20), [-0.8333] * 4, 0.08, 64, dict(N=16)),
+    # NavigationEnv's reward branches on both sides (plant_nav_branches).  |v| == 0 at a step is dropped: the reward is taken on the
+    # post-step state, whose velocity is v + sum acc dt over eight sub-steps; with the 3-slot delay ring the first steps apply the zero
+    # action (far above hover thrust), and afterwards acc would have to vanish bit for bit in every sub-step, which no action reaches
+    "bptt_nav_branches": ("nav", ENV_DYN, dict(max_episode_steps=1000, target=[12., 0., 3.]), None, None, 12,
+                          dict(layout="hoverish", init="nav_branches")),
+    # BASELINE configs[2]'s dynamics: RK4 with per-agent drag coefficients (plant_drag; tape row S + 2), fast agents so that drag matters
+    "bptt_nav_rk4_drag": ("nav", dict(ENV_DYN, integrator="rk4", drag_random=0.5), dict(max_episode_steps=1000, target=[12., 0., 3.]),
+                          None, None, 12, dict(layout="hoverish", init="nav_branches", drag=0.5, seed=43)),
     # velocity / position action types have no BPTT fixture: the reference's autograd raises on them ("one of the variables
     # needed for gradient computation has been modified by an inplace operation": the per-agent loop of dynamics.py:446-450
     # / 481-488 writes pose_err[:, i] / ang_vel_err[:, i] in place while earlier slices are saved for backward), tried
@@ -665,11 +686,177 @@ BPTT_CASES = {
 }
 
 
+# what the probes of gen_bptt count, in live (= not done in that step) rotor-steps (thr_*), state-component-steps (v_*, w_*, pz_*) or
+# agent-steps (done_cut, gate_pass); "tie" = the pre-clamp value equals the limit bit for bit (torch passes the gradient there)
+HIT_NAMES = ("thr_lo", "thr_hi", "thr_free", "thr_tie_lo", "thr_tie_hi", "v_lo", "v_hi", "w_lo", "w_hi", "pz_lo", "pz_hi",
+             "done_cut", "gate_pass",
+             # NavigationEnv.get_reward (NavigationEnv.py:85-99), live agent-steps per side of each branch: closing speed above / not above
+             # the clamp_max 10; view angle acos(.) at least / below pi / 18; |v| == 0; 1 - collision_dis positive / not (first relu);
+             # approach speed <cv, v> / (1e-6 + dis) positive / not (second relu)
+             "nav_close_hi", "nav_close_lo", "nav_view_hi", "nav_view_lo", "nav_v_zero", "nav_near_hi", "nav_near_lo", "nav_appr_hi", "nav_appr_lo")
+NAV_SIDES = HIT_NAMES[13:]
+
+
+class _Probe:
+    """records, from the reference's own tensors while it steps, the argument of the thrust clamp (dynamics.py:501), the state in
+    front of _ugly_fix (:374-382) and the full state behind it (= the post-step state, before any auto-reset)"""
+
+    def __init__(self, env):
+        self.traw, self.pre, self.state = [], [], []
+        self.dyn = dyn = env.envs.dynamics
+        get, fix = dyn._get_thrust_from_cmd, dyn._ugly_fix
+
+        def spy_get(command):
+            real = th.clamp
+
+            def spy(x, *a, **k):
+                self.traw.append(x.detach().clone().T)                 # (N, 4)
+                return real(x, *a, **k)
+            th.clamp = spy
+            try:
+                return get(command)
+            finally:
+                th.clamp = real
+
+        def spy_fix():
+            self.pre.append(th.cat([dyn._position.detach().clone(), dyn._velocity.detach().clone(),
+                                    dyn._angular_velocity.detach().clone()]).T)       # (N, 9)
+            fix()
+            self.state.append(dyn.full_state.detach().clone())
+
+        dyn._get_thrust_from_cmd, dyn._ugly_fix = spy_get, spy_fix
+        self.nav = []
+        if type(env).__name__ == "NavigationEnv":
+            reward = env.get_reward
+
+            def spy_reward(*a, **k):      # the branch arguments, by the expressions of NavigationEnv.py:90-96 on the env's own tensors
+                with th.no_grad():
+                    tp = env.target - env.position
+                    close = (env.velocity * tp).sum(dim=1) / (1e-6 + tp.norm(dim=1))
+                    vn = env.velocity.norm(dim=1)
+                    view = ((env.direction * env.velocity).sum(dim=1) / (1e-6 + vn)).clamp(-1., 1.).acos()
+                    near = 1 - env.collision_dis
+                    appr = (env.collision_vector * env.velocity).sum(dim=1) / (1e-6 + env.collision_dis)
+                    self.nav.append(th.stack([close > 10, close <= 10, view >= th.pi / 18, view < th.pi / 18, vn == 0,
+                                              near > 0, near <= 0, appr > 0, appr <= 0], dim=1).clone())
+                return reward(*a, **k)
+            env.get_reward = spy_reward
+
+    def sides(self, consts):
+        """-1 / 0 / +1 per clamp: below the interval, inside it (ties included), above it -> (H, N, 13) int8"""
+        traw, pre = th.stack(self.traw).double().numpy(), th.stack(self.pre).double().numpy()
+        bd = self.dyn._bd_thrust        # this run's own bounds: a tie of the fp32 run is not one in double
+        lo = np.concatenate([np.full(4, float(bd.min)), [-100, -100, 0], [-20] * 3, [-10] * 3])
+        hi = np.concatenate([np.full(4, float(bd.max)), [100, 100, 20], [20] * 3, [10] * 3])
+        x = np.concatenate([traw, pre], axis=2)
+        s = (x > hi).astype(np.int8) - (x < lo).astype(np.int8)
+        if self.nav:      # (get_reward is also called by reset(): the last H calls are the steps')
+            s = np.concatenate([s, th.stack(self.nav[-s.shape[0]:]).numpy().astype(np.int8)], axis=2)
+        return s, traw, pre
+
+
+def sat_actions(rng, H, N, consts, layout):
+    """actions that reach both thrust clamps.  "thrust": per rotor, 55 % uniform below the action at which m (a acc_half + acc_mean)
+    reaches T_max, 45 % uniform above it; "full": uniform over [-1, 1] on all four components.  Then planted entries: 4 % exactly
+    -1.0f (Traw == T_min bit for bit, checked here), 4 % exactly +1.0f and, where one exists, the fp32 action with Traw == T_max on
+    30 % of the entries of the first N // 12 agents"""
+    m, half, mean = (np.float32(consts[k]) for k in ("m", "acc_half", "acc_mean"))
+    T_min, T_max = np.float32(consts["T_min"]), np.float32(consts["T_max"])
+    traw = lambda a: m * (np.float32(a) * half + mean)
+    a_hi = np.float32((float(T_max) / float(m) - float(mean)) / float(half))
+    if layout == "hoverish":     # the classic layout (hover action + noise), no planted entries
+        return decode_actions(rng.integers(-127, 128, size=(H, N, 4), dtype=np.int8), [-0.3, 0, 0, 0], 0.5), None
+    if layout == "thrust":
+        u = rng.uniform(size=(H, N, 4))
+        a = np.where(u < 0.55, rng.uniform(-1, a_hi, size=(H, N, 4)), rng.uniform(a_hi, 1, size=(H, N, 4))).astype(np.float32)
+    else:
+        a = rng.uniform(-1, 1, size=(H, N, 4)).astype(np.float32)
+    assert traw(-1.0) == T_min, "Traw(-1.0f) is not T_min: plant the action for which it is"
+    tie_hi = None
+    c = a_hi
+    for _ in range(64):      # the fp32 neighbours of the real-valued solution
+        c = np.nextafter(c, np.float32(-2))
+    for _ in range(128):
+        if traw(c) == T_max:
+            tie_hi = c
+            break
+        c = np.nextafter(c, np.float32(2))
+    r = rng.uniform(size=(H, N, 4))
+    a[r < 0.04] = np.float32(-1.0)
+    a[(r >= 0.04) & (r < 0.08)] = np.float32(1.0)
+    if tie_hi is not None and layout == "thrust":     # on the first N // 12 agents only: the double-precision run cannot tie there
+        a[:, :max(1, N // 12)][r[:, :max(1, N // 12)] >= 0.7] = tie_hi
+    return np.clip(a, np.float32(-1), np.float32(1)).astype(np.float32), tie_hi
+
+
+def plant_state_clamps(rng, fs, consts):
+    """initial states from which _ugly_fix clips within the first steps, on a HoverEnv with is_collision_reset=False:
+    agents 0-11 v_x = v_y = +23..26 and agents 40-63 v_x = +23..26 (drag brings them below 20 after the first step), 12-23 v_y = -(23..26), 24-31 v_z = -(21..24) from 6 m (gravity keeps them beyond -20);
+    agents 8-23 start 3 cm above the floor sinking at 2 m/s (p_z clips at 0 from the first step on; out-of-bounds is a strict
+    comparison, droneEnv.py:361, and the collision this is does not end the episode with is_collision_reset=False);
+    agents 16-39 all three body rates +(10.5..14), 40-63 -(10.5..14)."""
+    fs = fs.copy()
+    N = fs.shape[0]
+    u = lambda lo, hi, n: rng.uniform(lo, hi, size=n).astype(np.float32)
+    fs[0:12, 7] = u(23, 26, 12)
+    fs[0:12, 8] = u(23, 26, 12)
+    fs[40:N, 7] = u(23, 26, N - 40)
+    fs[12:24, 8] = -u(23, 26, 12)
+    fs[24:32, 9] = -u(21, 24, 8)
+    fs[24:32, 2] = 6.0
+    fs[8:24, 2] = 0.03
+    fs[8:24, 9] = -2.0
+    fs[16:40, 10:13] = u(10.5, 14, (24, 3))
+    fs[40:N, 10:13] = -u(10.5, 14, (N - 40, 3))
+    return fs
+
+
+def plant_nav_branches(rng, fs, consts):
+    """initial states for NavigationEnv with the target 12 m ahead (no success, no collision inside the horizon), so that live agents
+    take each reward branch on both sides: agents 0-15 fly at the target at 12..18 m/s, nose along the velocity within a few degrees
+    (closing speed above the clamp_max 10; view angle below pi / 18); the rest are slow with random headings (below 10; above pi / 18);
+    agents 16-31 start 0.45..0.8 m above the floor (1 - collision_dis > 0), 16-23 sinking, 24-31 climbing (approach speed on either
+    side of its relu); everybody else is more than 1 m from every face.  |v| == 0 is not planted: see the case."""
+    fs = fs.copy()
+    N = fs.shape[0]
+    u = lambda lo, hi, n: rng.uniform(lo, hi, size=n).astype(np.float32)
+    fs[:, 0], fs[:, 1], fs[:, 2] = u(0, 2, N), u(-2, 2, N), u(2.5, 4.5, N)
+    fs[:, 3:7] = [1, 0, 0, 0]
+    fs[:, 7:10] = u(-1.5, 1.5, (N, 3))
+    fs[:, 10:13] = u(-0.3, 0.3, (N, 3))
+    yaw = u(-np.pi, np.pi, N - 16)
+    fs[16:, 3], fs[16:, 6] = np.cos(yaw / 2), np.sin(yaw / 2)
+    fs[0:16, 7], fs[0:16, 8], fs[0:16, 9] = u(12, 18, 16), u(-0.3, 0.3, 16), u(-0.2, 0.2, 16)
+    fs[16:32, 2] = u(0.45, 0.8, 16)
+    fs[16:24, 9] = -u(0.2, 0.6, 8)
+    fs[24:32, 9] = u(0.5, 1.5, 8)
+    return fs
+
+
+def plant_drag(rng, dyn, r=0.5):
+    """per-agent drag factors by the expression of Dynamics.reset (dynamics.py:245-246) on (3, N) draws: the reference's full reset
+    draws ONE factor pair for all agents and its indexed reset raises (SURVEY C-2), so per-agent coefficients are planted"""
+    N = dyn.num
+    for attr in ("_linear_drag_coeffs", "_quad_drag_coeffs"):
+        mean = getattr(dyn, attr + "_mean")
+        draw = th.from_numpy(rng.uniform(size=(3, N)).astype(np.float32)).to(mean.dtype)
+        setattr(dyn, attr, mean * (((draw - 0.5) * 2 * r).clamp(-0.5, .5) + 1))
+
+
 def gen_bptt(name, N=64, seed=42):
     """dLoss/dAction through H env steps of the reference with requires_grad=True (torch autograd over
-    Dynamics.step + reward; BPTT.py:107-134), loss = sum_t <Wr[t], reward_t> + <Wo[t], obs_t>."""
+    Dynamics.step + reward; BPTT.py:107-134), loss = sum_t <Wr[t], reward_t> + <Wo[t], obs_t>.
+
+    Cases with an options dict (the saturation / clamp cases) also store the post-step full state of every step, the probe counts
+    `hits` (HIT_NAMES) and `noise_rel`: the roll-out is repeated in DOUBLE precision (torch's default dtype switched; the reference
+    hard-codes no fp32 tensor on this path) from the same initial state, actions, weights and re-spawn states, the agents whose done
+    flags and clamp sides equal the fp32 run's are kept (>= 90 % required), and noise_rel is the largest |g32 - g64| over the judged agents
+    (stored as `judged`, see below) relative to the agent's own max|g64| -- the fp32 noise of the reference's own gradient, which sizes the per-agent test bound."""
     HoverEnvShim, NavigationEnv, RacingEnv = import_envs()
-    kind, dkw, kw, hover, scale, H = BPTT_CASES[name]
+    kind, dkw, kw, hover, scale, H, *rest = BPTT_CASES[name]
+    opts = rest[0] if rest else None
+    if opts:
+        N, seed = opts.get("N", N), opts.get("seed", seed)
     if dkw.get("integrator") == "rk4":
         repair_rk4("VisFly.utils.maths")
     use_cr_sqrt(True)
@@ -683,27 +870,48 @@ def gen_bptt(name, N=64, seed=42):
     kw = dict(kw)
     if "target" in kw:
         kw["target"] = th.tensor(kw["target"])
-    env = cls(num_agent_per_scene=N, num_scene=1, seed=seed, visual=False, dynamics_kwargs=dict(dkw), device="cpu",
-              requires_grad=True, **({"tensor_output": True} if kind.startswith("hover") else {}), **kw)
-    env.tensor_output = True
-    if kind == "racing":
-        env.targets = th.as_tensor(RACING_TEST_GATES)
+
+    def make_env():
+        e = cls(num_agent_per_scene=N, num_scene=1, seed=seed, visual=False, dynamics_kwargs=dict(dkw), device="cpu",
+                requires_grad=True, **({"tensor_output": True} if kind.startswith("hover") else {}),
+                **{k: (v.to(th.get_default_dtype()) if k == "target" else v) for k, v in kw.items() if k != "is_collision_reset"})
+        e.tensor_output = True
+        if "is_collision_reset" in kw:       # (HoverEnv's constructor does not pass it on; droneGymEnv.py:73,189 read the attribute)
+            e.is_collision_reset = kw["is_collision_reset"]
+        if kind == "racing":
+            e.targets = th.as_tensor(RACING_TEST_GATES)
+        return e
+
+    env = make_env()
     consts = extract_consts(env.envs.dynamics)
     rng = np.random.default_rng(seed + 5)
-    acts = th.tensor(decode_actions(rng.integers(-127, 128, size=(H, N, 4), dtype=np.int8), hover, scale),
-                     requires_grad=True)
+    tie_hi = None
+    if opts and opts.get("layout"):
+        a0, tie_hi = sat_actions(rng, H, N, consts, opts["layout"])
+    else:
+        a0 = decode_actions(rng.integers(-127, 128, size=(H, N, 4), dtype=np.int8), hover, scale)
+    acts = th.tensor(a0, requires_grad=True)
     Wr = th.tensor(rng.normal(size=(H, N)).astype(np.float32))
     Wo = th.tensor((rng.normal(size=(H, N, obs_w)) * 0.1).astype(np.float32))
     env.reset()
     dyn = env.envs.dynamics
+    if opts and opts.get("init"):      # planted initial state, through the reference's own reset-with-state (droneGymEnv.py:339-349)
+        plant = {"state_clamps": plant_state_clamps, "nav_branches": plant_nav_branches}[opts["init"]]
+        env.reset_agent_by_id(None, state=th.from_numpy(plant(rng, f32(dyn.full_state), consts)))
+    if opts and opts.get("drag"):
+        plant_drag(rng, dyn, opts["drag"])
+        drag = (f32(dyn._linear_drag_coeffs.T), f32(dyn._quad_drag_coeffs.T))
+    probe = _Probe(env) if opts else None
     fs_init = f32(dyn.full_state)
     gate0 = env._next_target_i.clone().numpy().astype(np.int32) if kind == "racing" else None
     loss = 0
-    dones, rewards, ev_step, ev_agent, ev_fs = [], [], [], [], []
+    dones, rewards, ev_step, ev_agent, ev_fs, passes = [], [], [], [], [], []
     for t in range(H):
         o, r, d, info = env.step(acts[t])
         loss = loss + (Wr[t] * r).sum() + (Wo[t] * o["state"]).sum()
         dones.append(d.numpy().astype(np.uint8)); rewards.append(f32(r))
+        if kind == "racing":
+            passes.append(env._is_pass_next.clone().numpy().astype(np.uint8))
         didx = np.nonzero(d.numpy())[0]
         if len(didx):
             fs = f32(dyn.full_state)
@@ -723,6 +931,72 @@ def gen_bptt(name, N=64, seed=42):
     if kind == "racing":
         save.update(gates=np.asarray(RACING_TEST_GATES, np.float32), gate0=gate0)
     save.update({"c_" + k: v for k, v in consts.items()})
+    if opts:
+        done = np.stack(dones).astype(bool)
+        live = ~done
+        sides, traw, pre = probe.sides(consts)
+        T_min, T_max = float(consts["T_min"]), float(consts["T_max"])
+        lr, l3 = live[:, :, None] & np.ones(4, bool), live[:, :, None] & np.ones(3, bool)
+        cnt = {"thr_lo": (sides[..., :4] < 0) & lr, "thr_hi": (sides[..., :4] > 0) & lr,
+               "thr_free": (traw > T_min) & (traw < T_max) & lr, "thr_tie_lo": (traw == T_min) & lr, "thr_tie_hi": (traw == T_max) & lr,
+               "v_lo": (sides[..., 7:10] < 0) & l3, "v_hi": (sides[..., 7:10] > 0) & l3,
+               "w_lo": (sides[..., 10:13] < 0) & l3, "w_hi": (sides[..., 10:13] > 0) & l3,
+               "pz_lo": (sides[..., 6] < 0) & live, "pz_hi": (sides[..., 6] > 0) & live, "done_cut": done,
+               "gate_pass": (np.stack(passes).astype(bool) & live) if passes else np.zeros(1, bool)}
+        for j, k in enumerate(NAV_SIDES):
+            cnt[k] = (sides[..., 13 + j] != 0) & live if sides.shape[2] > 13 else np.zeros(1, bool)
+        hits = np.asarray([int(cnt[k].sum()) for k in HIT_NAMES], np.int64)
+        print("   hits:", ", ".join(f"{k} {v}" for k, v in zip(HIT_NAMES, hits)))
+        # ---- the same roll-out in double precision ----
+        th.set_default_dtype(th.float64)
+        try:
+            env64 = make_env()
+            env64.reset()
+            env64.reset_agent_by_id(None, state=th.from_numpy(fs_init).double())
+            if kind == "racing":
+                env64._next_target_i = th.from_numpy(gate0).to(env64._next_target_i.dtype)
+            if opts.get("drag"):
+                d64 = env64.envs.dynamics
+                d64._linear_drag_coeffs, d64._quad_drag_coeffs = (th.from_numpy(x.T.copy()).double() for x in drag)
+            p64 = _Probe(env64)
+            a64 = th.tensor(f32(acts).astype(np.float64), requires_grad=True)
+            Wr64, Wo64 = Wr.double(), Wo.double()
+            es, ea = np.asarray(ev_step), np.asarray(ev_agent)
+            loss64, done64 = 0, []
+            for t in range(H):
+                o, r, d, _ = env64.step(a64[t], is_test=True)
+                done64.append(d.numpy().astype(bool))
+                sel = es == t
+                if sel.any():    # scripted re-spawns: the fp32 run's agents and states; the step returns the observation AFTER them
+                    o = env64.reset_agent_by_id(th.from_numpy(ea[sel].astype(np.int64)), state=th.from_numpy(np.stack(ev_fs)[sel]).double())
+                loss64 = loss64 + (Wr64[t] * r).sum() + (Wo64[t] * o["state"]).sum()
+            loss64.backward()
+        finally:
+            th.set_default_dtype(th.float32)
+        g64 = a64.grad.numpy()
+        sides64, _, _ = p64.sides(consts)
+        same = (np.stack(done64) == done).all(0) & (sides64 == sides).all((0, 2))
+        own = np.abs(g64).max((0, 2))
+        scale64 = own.max()
+        err = np.abs(g.astype(np.float64) - g64).max((0, 2))
+        # judged agents (stored; the test holds exactly these to the per-agent bound): same sides in double, own scale at least 1e-3 of
+        # the global one IN THE FP32 GRADIENT (the quantity the test has), and no planted Traw == T_max tie.  A tie is a property of the
+        # fp32 roll-out only (in double the same action lands strictly inside or outside), and on the thrust fixtures the largest
+        # fp32-vs-double difference, 4e-3 of the agent's own scale, sits at step 0 of one tie-carrying agent while every other agent and
+        # step is at 1e-6; its cause beyond that is not established, so the tie carriers stay under the global bound alone
+        tie_agent = (cnt["thr_tie_hi"]).any((0, 2))
+        own32 = np.abs(g).max((0, 2))
+        judged = same & (own32 >= 1e-3 * np.abs(g).max()) & ~tie_agent & (own > 0)
+        noise_rel = float((err[judged] / own[judged]).max())
+        print(f"   double run: {int(same.sum())} of {N} agents take the same sides, {int(judged.sum())} judged; noise_rel {noise_rel:.3e} "
+              f"(global {err[same].max() / scale64:.3e}; tie carriers {err[tie_agent].max() / scale64 if tie_agent.any() else 0:.3e})")
+        assert same.mean() >= 0.9, "fewer than 90 % of the agents take the same sides in double: pick another seed"
+        save.update(state=np.stack([f32(x) for x in probe.state]), hits=hits, hit_names=np.asarray(HIT_NAMES),
+                    noise_rel=np.float64(noise_rel), same64=same.astype(np.uint8), judged=judged.astype(np.uint8),
+                    is_collision_reset=np.uint8(kw.get("is_collision_reset", True)),
+                    tie_hi_action=np.float32(np.nan if tie_hi is None else tie_hi))
+        if opts.get("drag"):
+            save.update(drag_lin=drag[0], drag_quad=drag[1])
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **save)
 
 
@@ -891,7 +1165,11 @@ def gen_ckpt_keys(name="ckpt_keys"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
+    ap.add_argument("--out", default=None, help="write the fixtures here instead of tests/golden")
     args = ap.parse_args()
+    if args.out:
+        global OUT
+        OUT = args.out
     os.makedirs(OUT, exist_ok=True)
     for name in DYN_CASES:
         if args.only in (None, name):
