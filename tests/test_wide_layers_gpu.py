@@ -39,8 +39,20 @@ def test_wide_linear_entry_points_vs_torch_fp64(K, No, M):
     for every activation kind; every call made twice -> bit-identical outputs.  The saved output handed to the gradient entry points is
     the fp64 reference's, rounded to fp32 (as test_linear_layers_vs_torch does): a ReLU unit within fp32 rounding of zero then has the
     same side in kernel and reference, and the comparison is of the products alone."""
+    assert L()[1].vf_linear_is_wide(K, No) == 1
+    _check_linear_entry_points(K, No, M)
+
+
+@pytest.mark.parametrize("K,No,wide", [(128, 128, 0), (160, 128, 1)])
+def test_linear_entry_points_on_both_sides_of_the_dispatch(K, No, wide):
+    """the same checks one step either side of the narrow / wide predicate, at M = 70: one full 64-row tile plus a ragged one for the
+    weight-stationary kernels, more than one partial for the shared fold after the streamed-operand weight gradient"""
+    assert L()[1].vf_linear_is_wide(K, No) == wide
+    _check_linear_entry_points(K, No, 70)
+
+
+def _check_linear_entry_points(K, No, M):
     _lib, lib = L()
-    assert lib.vf_linear_is_wide(K, No) == 1
     g = torch.Generator(device=DEV).manual_seed(K * 1000 + No + M)
     X = torch.randn((M, K), device=DEV, generator=g)
     W = torch.randn((No, K), device=DEV, generator=g) / np.sqrt(K)

@@ -1,4 +1,4 @@
-// clip_grad_norm_ + torch.optim.Adam (weight decay as L2) on one parameter: the arithmetic of k_adam (vf_ppo.hip).
+// clip_grad_norm_ + torch.optim.Adam (weight decay as L2) on one parameter: the arithmetic of k_adam (vf_optim.hip).
 // Reference: utils/algorithms/PPO.py:285-292 (clip_grad_norm_, optimizer.step()).
 #pragma once
 #include <cmath>

@@ -44,6 +44,13 @@ constexpr int kBlock = 256;  // 4 wave64 per workgroup
 
 inline int blocks_for(int n) { return (n + kBlock - 1) / kBlock; }
 
+// blocks of a grid-stride launch over n elements, at most `cap`
+inline int grid_for(long n, int cap = 512)
+{
+    long b = (n + kBlock - 1) / kBlock;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 // Kernel shape per launch: while one-thread-per-agent work cannot even give every SIMD a wave
 // (<= 32768 agents) the two-wave split (rotation | translation on co-resident waves) wins; from one
 // wave per SIMD on, the plain kernel issues fewer instructions in total and has no hand-off barriers.
@@ -66,6 +73,20 @@ struct vf_env_dev {
 // `e` must be the handle's device block (what the step / roll-out kernels get through their pointer argument), NOT a by-value copy
 // of a vf_env_cfg: k_env_reset takes the value in its argument struct instead
 __device__ __forceinline__ unsigned env_agent0(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_dev&>(e).agent0; }
+
+// ---- wave64 reductions: fixed shuffle tree, the sum lands in lane 0 ----
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    return x;
+}
+__device__ __forceinline__ float wave_sumf(float x)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    return x;
+}
 
 // ---- Philox4x32-10 counter RNG (on-device spawner, exploration noise of the policy head) ----
 struct U4 {
@@ -238,8 +259,19 @@ int mlp_wgrad_fold_blocks(const vf_mlp_bwd_desc* d);
 int mlp_wgrad_launch(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, double* sq_part,
                      const vf_stats_fold* loss_stats, hipStream_t st);
 int mlp_wgrad_launch_layers(const vf_mlp_bwd_desc* d, float* partials, float* grad, int M, int accumulate, unsigned layer_mask, hipStream_t st);
-// vf_linear_wide.hip: the streamed-operand kernels behind vf_linear_* for layers the weight-stationary kernels cannot hold.
-// The one predicate every entry point dispatches on (exported as vf_linear_is_wide): up to 128 x 128 the old kernels keep serving
+// vf_mlp_tile.hip: validation of the layer tables, `who` = the entry point named in the message.  check_fwd_desc always tests the
+// layer count; kFwdDescInputs adds the input count, kFwdDescDims every layer's K, No in 1..kLinearNarrowMax
+enum { kFwdDescInputs = 1, kFwdDescDims = 2 };
+int check_fwd_desc(const vf_mlp_desc* desc, const char* who, int flags = 0);
+int check_bwd_desc(const vf_mlp_bwd_desc* desc, const char* who);
+// vf_optim.hip: sum and sum of squares of x[0..n) in fp64 (k_sum2_partial / k_sum2_final); part = 2 * 256 doubles of scratch,
+// out2 = {sum, sumsq} and / or out_ss_f32 = (float)sumsq.  Launches only: the caller checks hipGetLastError
+void sum2_launch(const float* x, long n, double* part, double* out2, float* out_ss_f32, hipStream_t st);
+// vf_linear.hip: k_fold_partials -- dW[0..nw), db[0..nb) (=|+=) the sum over nblk partial rows of `stride` floats, in a fixed order.
+// Launches only: the caller checks hipGetLastError
+void fold_partials_launch(const float* part, int nblk, int stride, int nw, int nb, float* dW, float* db, int accumulate, hipStream_t st);
+// vf_linear_wide.hip: the streamed-operand kernels behind vf_linear_* for layers the weight-stationary kernels of vf_linear.hip cannot
+// hold.  The one predicate vf_linear.hip dispatches on (exported as vf_linear_is_wide): up to 128 x 128 the old kernels keep serving
 constexpr int kLinearNarrowMax = 128, kLinearWideMax = 512;
 inline bool linear_is_wide(int K, int No) { return K > kLinearNarrowMax || No > kLinearNarrowMax; }
 int linear_wide_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, int M, int K, int No, int act, hipStream_t st);

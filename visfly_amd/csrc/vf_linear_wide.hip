@@ -1,4 +1,4 @@
-// Linear layers wider than the weight-stationary kernels of vf_ppo.hip can hold (128 < K or No <= 512), fp32 MFMA.
+// Linear layers wider than the weight-stationary kernels of vf_linear.hip can hold (128 < K or No <= 512), fp32 MFMA.
 //
 // k_linear / k_linear_wgrad keep the whole weight matrix of a layer in LDS; 256 x 256 fp32 is 256 KiB and the CU has 160.  Here
 // nothing is resident: a workgroup owns one 128 x 128 tile of the product, both operands are streamed through LDS in chunks of 32
@@ -16,7 +16,7 @@
 //   weight grad   No x K        rows of M   dYm [m][n]  red-major    X [m][k]  red-major
 // dYm = dY * act'(Y) is formed while the chunk is written to LDS (act_mul of vf_common.hpp, as the narrow kernels do).
 // The weight gradient splits M into row ranges: every workgroup writes the partial of its range to part[split][No*K + No] and
-// k_fold_partials (vf_ppo.hip) adds them in a fixed order - no floating-point atomics, bit-identical from run to run.
+// k_fold_partials (vf_linear.hip) adds them in a fixed order - no floating-point atomics, bit-identical from run to run.
 #include "vf_common.hpp"
 
 namespace vf {

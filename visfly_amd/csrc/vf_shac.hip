@@ -1,6 +1,6 @@
 // SHAC glue kernels (utils/algorithms/shac.py:215-278 on utils/policies/td_policies.py:82-252): everything of one SHAC
-// iteration that is neither the env step / its adjoint (vf_env.hip, vf_env_bwd.hip), the MLP forward / backward (vf_ppo.hip)
-// nor TD-lambda (k_td_returns in vf_ppo.hip):
+// iteration that is neither the env step / its adjoint (vf_env.hip, vf_env_bwd.hip), the MLP forward / backward (vf_linear.hip,
+// vf_mlp_tile.hip, vf_mlp_chain.hip) nor TD-lambda (k_td_returns in vf_bptt_ops.hip):
 //   k_shac_head_fwd / _bwd   the Actor's action head with its STATE-DEPENDENT log_std (td_policies.py:230-243):
 //                            a = tanh(mu + exp(clamp(log_std, -10, 2)) * eps) and its reverse
 //   k_shac_accumulate        actor-loss bookkeeping of one horizon step incl. the bootstrap term (shac.py:247-257) and the
