@@ -746,6 +746,11 @@ int vf_head_sample(const float* mean, const float* log_std, float* action, float
  * row0 (vf_env_set_agent_offset).  row0 + M <= 2^32. */
 int vf_head_sample_at(const float* mean, const float* log_std, float* action, float* log_prob, int32_t M, uint64_t row0,
                       uint64_t seed, uint64_t step, int32_t deterministic, vf_stream_t stream);
+/* the same head with the caller's standard-normal rows eps (M x 4) in place of the Philox draw: action and log-prob come from the
+ * device function vf_head_sample_at evaluates after its draw.  How a recorded roll-out's noise is replayed (PPO.collect_rollouts
+ * (replay=...)).  mean, eps and action 16-byte aligned. */
+int vf_head_sample_eps(const float* mean, const float* log_std, const float* eps, float* action, float* log_prob, int32_t M,
+                       vf_stream_t stream);
 /* Per-agent standard-normal rows for the trainers that take their exploration noise as a tensor (BPTT, SHAC):
  * eps[t][i][0..3] (T x N x 4 floats, 16-byte aligned) = the four Box-Muller normals of ONE Philox4x32-10 block with counter
  * {row0 + i, step0 + t} and key `seed` -- the arithmetic of vf_head_sample's noise under a domain tag of its own, so the two

@@ -26,7 +26,10 @@ The minibatch permutation: the reference's ``DictRolloutBuffer.get`` draws ``th.
 ``PPO`` instantiates through ``ori_PPO._setup_model``).  The generator provides the attribute as a feed of recorded permutations, so
 that the fixture carries them; rows are SB3's ``swap_and_flatten`` order (env-major: row = env * n_steps + step).
 
-Usage:  python oracle/gen_ppo_loop.py
+``gen_ppo_rollout`` (fixture ppo_rollout_nav) records the other half of ``PPO.learn``: SB3's ``collect_rollouts``, restated, on the
+reference's own NavigationEnv, policy and ``compute_returns_and_advantage`` -- see its docstring.
+
+Usage:  python oracle/gen_ppo_loop.py [--only NAME]
 """
 import os
 import sys
@@ -413,6 +416,191 @@ def gen_ppo_loop(name, T=8, N=64, batch_size=160, n_epochs=2, seed=21, lr=1e-3, 
         **rollout)
 
 
+# the spawn box of the roll-out fixture: reaches down to the floor (collisions within the first steps = non-truncated episode ends)
+ROLLOUT_SPAWN = {"state_generator": {"class": "Uniform", "kwargs": [{"position": {"mean": [1., 0., 0.7], "half": [1.0, 1.0, 0.65]}}]}}
+
+
+def gen_ppo_rollout(name="ppo_rollout_nav", T=32, N=64, max_episode_steps=10, seed=31, n_rollouts=2):
+    """The ROLL-OUT half of ``PPO.learn``: two consecutive runs of SB3's ``OnPolicyAlgorithm.collect_rollouts`` (restated below, marked
+    [SB3 2.2.1]) on the reference's own ``NavigationEnv`` (stub-imported, CR patches on as in ``gen_golden.gen_env``, tensor_output),
+    the reference's own ``CustomMultiInputActorCriticPolicy`` (constructed as in ``gen_ppo_loop``) and the reference's own
+    ``DictRolloutBuffer.compute_returns_and_advantage``.  The policy is built BEFORE the env is constructed and seeded and its noise
+    comes from a numpy feed through ``_standard_normal``, so the global torch stream is consumed by the env alone, in the order
+    ``spawn="replay"`` replays.  What goes where it would not go by itself:
+      * the rows are written where ``add()`` would put them (see gen_ppo_loop: the tensor port's add() cannot run);
+      * ``compute_returns_and_advantage`` receives ``dones`` as a float32 numpy array, as in gen_ppo_loop (``1.0 - dones`` is not
+        defined for the bool tensor a tensor_output env returns).
+    Next to the fp32 run the same policy is evaluated in float64 on the same observation rows and noise (``value_fp64``,
+    ``log_prob_fp64``, ``last_value_fp64``): the distance between the two sizes the tolerances of the GPU test."""
+    import copy
+    sp = _install_ppo_sb3()
+    _, NavigationEnv, _ = G.import_envs()
+    import VisFly.utils.algorithms.common as RC
+    import VisFly.utils.policies.policies as RPOL
+    import VisFly.utils.policies.extractors as E
+    G.use_cr_sqrt(True)
+
+    gamma, lam = 0.99, 0.95
+    obs_space = sp.Dict({"state": sp.Box(-1, 1, (13,)), "target": sp.Box(-1, 1, (3,))})
+    act_space = sp.Box(-1, 1, (4,))
+    th.manual_seed(seed)
+    policy = RPOL.CustomMultiInputActorCriticPolicy(
+        obs_space, act_space, lr_schedule=(lambda _: 1e-3), net_arch=dict(pi=[64, 64], vf=[64, 64]), activation_fn=nn.ReLU, ortho_init=False,
+        log_std_init=-0.5, features_extractor_class=E.StateTargetExtractor,
+        features_extractor_kwargs={"net_arch": {"state": {"layer": [128, 64]}, "target": {"layer": [128, 64]}}, "activation_fn": nn.ReLU},
+        optimizer_kwargs={"weight_decay": 1e-5})
+    assert type(policy.action_dist).__name__ == "SquashedDiagGaussianDistribution" and policy.share_features_extractor
+    with th.no_grad():
+        policy.action_net.weight.mul_(0.3)
+    params0 = _flat(policy)
+    policy64 = copy.deepcopy(policy).double()
+
+    rng = np.random.default_rng(seed + 9)
+    eps_all = rng.standard_normal((n_rollouts, T, N, 4)).astype(np.float32)
+    import torch.distributions.normal as TDN
+    feed = {"eps": None}
+
+    def fed_standard_normal(shape, dtype, device):
+        assert tuple(shape) == (N, 4), shape
+        return th.from_numpy(feed["eps"].copy()).to(dtype)
+    real_sn = TDN._standard_normal
+    TDN._standard_normal = fed_standard_normal
+
+    # ---- the env: constructed and seeded AFTER the policy; manual_seed(seed) (Dynamics.__init__) -> reset() -> the roll-outs ----
+    env = NavigationEnv(num_agent_per_scene=N, num_scene=1, seed=seed, visual=False, dynamics_kwargs=dict(G.ENV_DYN), device="cpu",
+                        max_episode_steps=max_episode_steps, random_kwargs=ROLLOUT_SPAWN)
+    env.tensor_output = True
+    consts = G.extract_consts(env.envs.dynamics)
+    dyn = env.envs.dynamics
+
+    # ---- [SB3 2.2.1] common/policies.py: BasePolicy.obs_to_tensor / unscale_action, common/utils.py: obs_as_tensor (Dict observations) ----
+    def obs_to_tensor(observation):
+        observation = {k: np.array(v).reshape((-1, *obs_space[k].shape)) for k, v in observation.items()}
+        return {k: th.as_tensor(v) for k, v in observation.items()}, True
+
+    def unscale_action(scaled_action):
+        low, high = act_space.low, act_space.high
+        return low + (0.5 * (scaled_action + 1.0) * (high - low))
+
+    def obs_as_tensor(obs):
+        return {k: th.as_tensor(v) for k, v in obs.items()}
+
+    state = {"last_obs": env.reset(), "last_episode_starts": np.ones((N,), dtype=bool)}     # _setup_learn (common/base_class.py)
+    fs_init = G.f32(dyn.full_state).copy()
+    obs0_state = G.f32(state["last_obs"]["state"]).copy()
+
+    # ---- [SB3 2.2.1] common/on_policy_algorithm.py: OnPolicyAlgorithm.collect_rollouts (callback, gSDE and logging lines left out) ----
+    def collect_rollouts(buf, n_rollout_steps, rec, r):
+        n_steps = 0
+        buf.reset()
+        while n_steps < n_rollout_steps:
+            with th.no_grad():
+                obs_tensor = obs_as_tensor(state["last_obs"])
+                feed["eps"] = eps_all[r, n_steps]
+                actions, values, log_probs = policy(obs_tensor)
+                # (beside the run: the same policy in float64 on the same rows and noise)
+                a64, v64, lp64 = policy64({k: v.double() for k, v in obs_tensor.items()})
+            actions = actions.cpu().numpy()
+            # Rescale and perform action
+            clipped_actions = actions
+            if policy.squash_output:
+                # Unscale the actions to match env bounds if they were previously squashed (scaled in [-1, 1])
+                clipped_actions = unscale_action(clipped_actions)
+            else:
+                # Otherwise, clip the actions to avoid out of bound error
+                clipped_actions = np.clip(actions, act_space.low, act_space.high)
+            rec["actions_env"].append(np.asarray(clipped_actions, np.float32).copy())
+            new_obs, rewards, dones, infos = env.step(clipped_actions)
+            n_steps += 1
+            rec["rewards_raw"].append(G.f32(rewards).copy())
+            # Handle timeout by bootstraping with value function
+            for idx, done in enumerate(dones):
+                if done and infos[idx].get("terminal_observation") is not None and infos[idx].get("TimeLimit.truncated", False):
+                    terminal_obs = obs_to_tensor(infos[idx]["terminal_observation"])[0]
+                    with th.no_grad():
+                        terminal_value = policy.predict_values(terminal_obs)[0]
+                    # (SB3's rewards are a numpy array, which takes the 1-element tensor; the tensor_output env's are a tensor: same
+                    # float32 product, same float32 sum)
+                    rewards[idx] += (gamma * terminal_value).reshape(())
+                    rec["boot"].append((n_steps - 1, idx, G.f32(terminal_obs["state"][0]).copy(), np.float32(terminal_value.item())))
+            # rollout_buffer.add(self._last_obs, actions, rewards, self._last_episode_starts, values, log_probs): the rows, written where
+            # add() would put them
+            p = buf.pos
+            for k in buf.observations:
+                buf.observations[k][p] = th.as_tensor(state["last_obs"][k])
+            buf.actions[p] = th.as_tensor(actions.reshape((N, 4)))
+            buf.rewards[p] = th.as_tensor(rewards)
+            buf.episode_starts[p] = th.as_tensor(state["last_episode_starts"])
+            buf.values[p] = values.clone().flatten()
+            buf.log_probs[p] = log_probs.clone()
+            buf.pos += 1
+            buf.full = buf.pos == buf.buffer_size
+            state["last_obs"] = new_obs
+            state["last_episode_starts"] = dones
+            # (beside the run: what the fixture records of the step)
+            d = dones.numpy()
+            rec["done"].append(d.astype(np.uint8))
+            rec["trunc"].append(np.asarray([bool(d[i]) and bool(infos[i]["TimeLimit.truncated"]) for i in range(N)], np.uint8))
+            fs = G.f32(dyn.full_state)
+            for i in np.nonzero(d)[0]:
+                rec["ev_step"].append(n_steps - 1); rec["ev_agent"].append(i); rec["ev_fs"].append(fs[i].copy())
+            rec["value_fp64"].append(v64.flatten().numpy().copy()); rec["log_prob_fp64"].append(lp64.numpy().copy())
+            rec["action_fp64"].append(a64.numpy().copy())
+        with th.no_grad():
+            # Compute value for the last timestep
+            values = policy.predict_values(obs_as_tensor(new_obs))
+            rec["last_value_fp64"] = policy64.predict_values({k: v.double() for k, v in obs_as_tensor(new_obs).items()}).flatten().numpy().copy()
+        buf.compute_returns_and_advantage(last_values=values, dones=dones.numpy().astype(np.float32))
+        return values, dones
+
+    save = {}
+    total = {k: 0 for k in ("n_truncated", "n_not_truncated", "n_agents_two_ends", "n_end_last_step", "n_end_step0")}
+    for r in range(n_rollouts):
+        rec = {k: [] for k in ("actions_env", "rewards_raw", "boot", "done", "trunc", "ev_step", "ev_agent", "ev_fs", "value_fp64",
+                               "log_prob_fp64", "action_fp64")}
+        buf = RC.DictRolloutBuffer(T, obs_space, act_space, gae_lambda=lam, gamma=gamma, n_envs=N)
+        last_values, dones = collect_rollouts(buf, T, rec, r)
+        assert buf.full
+        done, trunc = np.stack(rec["done"]), np.stack(rec["trunc"])
+        cnt = dict(n_truncated=int(trunc.sum()), n_not_truncated=int((done & (1 - trunc)).sum()),
+                   n_agents_two_ends=int((done.sum(0) >= 2).sum()), n_end_last_step=int(done[T - 1].sum()), n_end_step0=int(done[0].sum()))
+        assert len(rec["boot"]) == cnt["n_truncated"]
+        for k, v in cnt.items():
+            total[k] += v
+        rewards, rewards_raw = G.f32(buf.rewards).copy(), np.stack(rec["rewards_raw"])
+        out = dict(
+            eps=eps_all[r], actions=G.f32(buf.actions).copy(), actions_env=np.stack(rec["actions_env"]),
+            obs_state=G.f32(buf.observations["state"]).copy(), obs_target=G.f32(buf.observations["target"]).copy(),
+            values=G.f32(buf.values).copy(), log_probs=G.f32(buf.log_probs).copy(), episode_starts=G.f32(buf.episode_starts).copy(),
+            rewards=rewards, rewards_raw=rewards_raw, done=done, truncated=trunc,
+            boot_step=np.asarray([b[0] for b in rec["boot"]], np.int32), boot_agent=np.asarray([b[1] for b in rec["boot"]], np.int32),
+            boot_state=np.stack([b[2] for b in rec["boot"]]), boot_value=np.asarray([b[3] for b in rec["boot"]], np.float32),
+            last_values=G.f32(last_values).reshape(N).copy(), dones=dones.numpy().astype(np.float32),
+            last_obs_state=G.f32(state["last_obs"]["state"]).copy(),
+            advantages=G.f32(buf.advantages).copy(), returns=G.f32(buf.returns).copy(),
+            ev_step=np.asarray(rec["ev_step"], np.int32), ev_agent=np.asarray(rec["ev_agent"], np.int32), ev_fs=np.stack(rec["ev_fs"]),
+            value_fp64=np.stack(rec["value_fp64"]), log_prob_fp64=np.stack(rec["log_prob_fp64"]), last_value_fp64=rec["last_value_fp64"], **{k: np.int32(v) for k, v in cnt.items()})
+        d = lambda a, b: float(np.abs(a.astype(np.float64) - b).max())
+        print(f"{name}[{r}]: {cnt}; fp32 vs fp64: value {d(out['values'], out['value_fp64']):.3e} log_prob {d(out['log_probs'], out['log_prob_fp64']):.3e} "
+              f"action {d(out['actions'], np.stack(rec['action_fp64'])):.3e} last_value {d(out['last_values'], out['last_value_fp64']):.3e}; "
+              f"|actions_env - actions| {d(out['actions_env'], out['actions']):.3e}; max|action| {np.abs(out['actions']).max():.6f}; "
+              f"max|value| {np.abs(out['values']).max():.3f} max|log_prob| {np.abs(out['log_probs']).max():.3f}; episode ends per step "
+              f"{done.sum(1).tolist()}, of them truncated {trunc.sum(1).tolist()}")
+        save.update({f"r{r}_{k}": v for k, v in out.items()})
+    TDN._standard_normal = real_sn
+    for k, v in total.items():
+        assert v >= 1, f"the fixture must contain every edge of the roll-out: {k} = {v}"
+    assert save["r1_episode_starts"][0].min() == 0.0, "the second roll-out starts inside running episodes"
+    np.savez_compressed(
+        os.path.join(OUT, name + ".npz"), params0=params0, fs_init=fs_init, obs0_state=obs0_state, seed=np.int32(seed), T=np.int32(T),
+        N=np.int32(N), n_rollouts=np.int32(n_rollouts), max_episode_steps=np.int32(max_episode_steps), gamma=np.float64(gamma),
+        gae_lambda=np.float64(lam), log_std_init=np.float64(-0.5), target=G.f32(env.target[0]), spawn=np.asarray(repr(ROLLOUT_SPAWN)),
+        dyn_kw=np.asarray(repr(dict(G.ENV_DYN))), action_branch=np.asarray("unscale_action" if policy.squash_output else "clip"),
+        label=np.asarray("SB3 2.2.1 OnPolicyAlgorithm.collect_rollouts (restated, oracle/gen_ppo_loop.py) on the reference's own NavigationEnv "
+                         "(cr-sqrt-oracle), CustomMultiInputActorCriticPolicy and DictRolloutBuffer.compute_returns_and_advantage"),
+        **{k: np.int32(v) for k, v in total.items()}, **save, **{"c_" + k: v for k, v in consts.items()})
+
+
 CASES = {
     "ppo_loop_nav": dict(),
     "ppo_loop_nav_kl": dict(seed=22, ent_coef=0.01, clip_range_vf=0.3, target_kl=None, lr=3e-3),      # target_kl filled in below
@@ -423,13 +611,16 @@ CASES = {
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default=None, choices=[None] + list(CASES))
+    ap.add_argument("--only", default=None, choices=[None] + list(CASES) + ["ppo_rollout_nav"])
     ap.add_argument("--target-kl", type=float, default=None)
+    ap.add_argument("--seed", type=int, default=None, help="ppo_rollout_nav: another seed (tuning the edge counts)")
     a = ap.parse_args()
     if a.only is None:         # separate interpreters: the run patches module-level state of torch and of the imported reference
         import subprocess
-        for n in CASES:
+        for n in list(CASES) + ["ppo_rollout_nav"]:
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--only", n])
+    elif a.only == "ppo_rollout_nav":
+        gen_ppo_rollout(a.only, **({} if a.seed is None else {"seed": a.seed}))
     else:
         kw = dict(CASES[a.only])
         if a.only == "ppo_loop_nav_kl":

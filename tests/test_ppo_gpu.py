@@ -995,9 +995,18 @@ def test_deferred_bootstrap_equals_per_step_bootstrap(env_name):
                                             ("HoverEnv", 1000, "euler_nodelay"), ("NavigationEnv", 16500, "rk4_nodelay"),
                                             ("HoverEnv2", 3000, "euler"), ("NavigationEnv2", 3000, "euler"), ("NavigationEnv2", 16500, "rk4"),
                                             ("NavigationEnv2", 3000, "euler_nodelay"),
-                                            ("RacingEnv", 3000, "euler"), ("RacingEnv2", 3000, "euler"), ("RacingEnv2", 16401, "rk4")])
+                                            ("RacingEnv", 3000, "euler"), ("RacingEnv2", 3000, "euler"), ("RacingEnv2", 16401, "rk4"),
+                                            ("NavigationEnv", 64, "euler")])
 def test_persistent_rollout_equals_the_per_step_loop(env_name, N, dyn):
-    _persistent_rollout_vs_loop(env_name, N, dyn)
+    kw = {}
+    if N == 64:
+        # the shape at which the launch-by-launch loop is pinned to the reference's collect_rollouts (tests/golden/ppo_rollout_nav.npz,
+        # tests/test_ppo_loop_gpu.py): its agent count (a ragged single workgroup), episode length and roll-out length
+        from _golden import load
+        fx = load("ppo_rollout_nav")
+        assert N == int(fx["N"])
+        kw = dict(max_episode_steps=int(fx["max_episode_steps"]), n_steps=int(fx["T"]))
+    _persistent_rollout_vs_loop(env_name, N, dyn, **kw)
 
 
 @pytest.mark.parametrize("env_name,N,dyn,net", [("NavigationEnv", 3000, "euler", "verdict"), ("HoverEnv", 16401, "rk4_nodelay", "one_layer_extractor"),
@@ -1020,7 +1029,7 @@ def test_persistent_rollout_of_a_generated_class_equals_the_per_step_loop(env_na
     assert _lib.lib().vf_chain_plugin_launches() > n0
 
 
-def _persistent_rollout_vs_loop(env_name, N, dyn, policy_kwargs=None):
+def _persistent_rollout_vs_loop(env_name, N, dyn, policy_kwargs=None, max_episode_steps=7, n_steps=20):
     """collect_rollouts as ONE launch (vf_ppo_rollout: 16 / 32 agents per wave for all n_steps, the same rows-per-wave chain
     vf_mlp_forward picks for N rows) leaves the rollout buffer, the TimeLimit list, the episode statistics, the episode
     outputs and the slab of the launch-by-launch loop, bit for bit -- over two consecutive rollouts with a training pass
@@ -1042,9 +1051,9 @@ def _persistent_rollout_vs_loop(env_name, N, dyn, policy_kwargs=None):
         if env_name == "NavigationEnv":
             kw["random_kwargs"] = {"state_generator": {"class": "Uniform", "kwargs": [{"position": {"mean": [1., 0., 1.5], "half": [0., 2., 1.]}}]}}
         # r05: the *2 variants (relative-position observation rows, NavigationEnv2's reward) run on the persistent launch too
-        env = getattr(E, env_name)(num_agent_per_scene=N, seed=5, dynamics_kwargs=dict(dkw), device=DEV, max_episode_steps=7,
+        env = getattr(E, env_name)(num_agent_per_scene=N, seed=5, dynamics_kwargs=dict(dkw), device=DEV, max_episode_steps=max_episode_steps,
                                    tensor_output=True, **kw)
-        ppo = PPO(env, n_steps=20, batch_size=N * 20 // (4 if N < 16000 else 20), n_epochs=1, seed=2,
+        ppo = PPO(env, n_steps=n_steps, batch_size=N * n_steps // (4 if N < 16000 else 20), n_epochs=1, seed=2,
                   policy_kwargs=policy_kwargs or dict(activation_fn="relu"))
         ppo.fused_rollout = fused
         out = {}

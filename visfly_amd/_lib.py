@@ -286,6 +286,7 @@ SIGNATURES = {
     "vf_mlp_weight_grad_sumsq": (C.c_int, [C.POINTER(MlpBwdDesc), _vp, _vp, C.c_int32, C.c_int32, _vp, C.POINTER(StatsFold), _vp]),
     "vf_head_sample": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _vp]),
     "vf_head_sample_at": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, _vp]),
+    "vf_head_sample_eps": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "vf_noise_fill": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
     "vf_env_set_agent_offset": (C.c_int, [_vp, C.c_int64]),
     "vf_env_agent_offset": (C.c_int64, [_vp]),

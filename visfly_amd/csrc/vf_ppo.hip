@@ -97,6 +97,21 @@ __global__ __launch_bounds__(kBlock) void k_head_sample(const float4* __restrict
     action[i] = a;
 }
 
+// the same head with the caller's noise rows instead of Philox (vf_head_sample_eps)
+__global__ __launch_bounds__(kBlock) void k_head_sample_eps(const float4* __restrict__ mean, const float* __restrict__ log_std,
+                                                            const float4* __restrict__ eps, float4* __restrict__ action,
+                                                            float* __restrict__ logp, int M)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M) return;
+    const float4 m4 = mean[i], e4 = eps[i];
+    const float mu[4] = {m4.x, m4.y, m4.z, m4.w}, e[4] = {e4.x, e4.y, e4.z, e4.w};
+    const float ls[4] = {log_std[0], log_std[1], log_std[2], log_std[3]};
+    float4 a;
+    logp[i] = head_row_from_noise(mu, ls, e, a);
+    action[i] = a;
+}
+
 // PPO clipped surrogate + value MSE + "entropy" (= mean log-prob for the squashed head), PPO.py:210-263
 __global__ __launch_bounds__(kBlock) void k_ppo_loss(const float4* __restrict__ mean, const float* __restrict__ value,
                                                      const float* __restrict__ log_std, const float4* __restrict__ action,
@@ -342,6 +357,19 @@ int vf_head_sample(const float* mean, const float* log_std, float* action, float
                    uint64_t step, int32_t deterministic, vf_stream_t stream)
 {
     return vf_head_sample_at(mean, log_std, action, log_prob, M, 0, seed, step, deterministic, stream);
+}
+
+int vf_head_sample_eps(const float* mean, const float* log_std, const float* eps, float* action, float* log_prob, int32_t M,
+                       vf_stream_t stream)
+{
+    if (!mean || !log_std || !eps || !action || !log_prob || M <= 0) return vf::fail(VF_EINVAL, "vf_head_sample_eps: bad argument");
+    if ((reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(action)) % 16)
+        return vf::fail(VF_EINVAL, "vf_head_sample_eps: mean, eps and action must be 16-byte aligned");
+    hipLaunchKernelGGL(vf::k_head_sample_eps, dim3(vf::blocks_for(M)), dim3(vf::kBlock), 0, vf::as_stream(stream),
+                       reinterpret_cast<const float4*>(mean), log_std, reinterpret_cast<const float4*>(eps),
+                       reinterpret_cast<float4*>(action), log_prob, M);
+    VF_HIP(hipGetLastError());
+    return VF_OK;
 }
 
 int vf_ppo_loss(const float* mean, const float* value, const float* log_std, const float* action, const float* old_log_prob,

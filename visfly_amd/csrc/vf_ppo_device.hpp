@@ -30,6 +30,20 @@ __device__ __forceinline__ float squashed_log_prob(const float* mu, const float*
     return lp;
 }
 
+// Squashed diagonal Gaussian head of one row, noise given: action = tanh(mean + exp(log_std) eps) -> log-prob of the action
+// (policies.py:177-181,219-220; SB3 SquashedDiagGaussianDistribution.sample / log_prob).  Every sampling path ends here:
+// head_sample_row below (Philox noise) and k_head_sample_eps (vf_ppo.hip: the caller's noise).
+__device__ __forceinline__ float head_row_from_noise(const float* mu, const float* ls, const float* e, float4& action)
+{
+    float a[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) a[d] = tanhf(mu[d] + expf(ls[d]) * e[d]);
+    float g[4];
+    const float lp = squashed_log_prob(mu, ls, a, g);
+    action = make_float4(a[0], a[1], a[2], a[3]);
+    return lp;
+}
+
 // Squashed diagonal Gaussian head for the row whose counter word is `row` (the row's index, plus the first global agent id where
 // the caller keys by global agent: vf_head_sample_at, vf_env_set_agent_offset) (policies.py:177-181, SB3 SquashedDiagGaussianDistribution): action = tanh(mean +
 // exp(log_std) eps), eps = Box-Muller over Philox(row, step; seed); -> log-prob of the action.  k_head_sample (vf_ppo.hip) and
@@ -39,20 +53,18 @@ __device__ __forceinline__ float head_sample_row(const float4 m4, const float* _
 {
     const float mu[4] = {m4.x, m4.y, m4.z, m4.w};
     const float ls[4] = {log_std[0], log_std[1], log_std[2], log_std[3]};
-    float a[4];
     if (deterministic) {
+        float a[4];
 #pragma unroll
         for (int d = 0; d < 4; ++d) a[d] = tanhf(mu[d]);
-    } else {
-        float e[4];
-        philox_normal4(row, step, kTagPpoNoise, seed, e);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) a[d] = tanhf(mu[d] + expf(ls[d]) * e[d]);
+        float g[4];
+        const float lp = squashed_log_prob(mu, ls, a, g);
+        action = make_float4(a[0], a[1], a[2], a[3]);
+        return lp;
     }
-    float g[4];
-    const float lp = squashed_log_prob(mu, ls, a, g);
-    action = make_float4(a[0], a[1], a[2], a[3]);
-    return lp;
+    float e[4];
+    philox_normal4(row, step, kTagPpoNoise, seed, e);
+    return head_row_from_noise(mu, ls, e, action);
 }
 
 // The part of a row's loss that needs the ACTION only (SquashedDiagGaussianDistribution.log_prob: gaussian_actions = atanh(clamp(a)),

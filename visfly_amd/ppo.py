@@ -1079,10 +1079,20 @@ class PPO:
         deterministic: a = tanh(mean)"""
         return self._act(obs, deterministic)[0], None
 
-    def collect_rollouts(self):
+    def collect_rollouts(self, replay=None):
         """SB3 OnPolicyAlgorithm.collect_rollouts: n_steps of policy -> env.step -> buffer, with the
-        TimeLimit bootstrap reward += gamma * V(terminal_obs) for truncated episodes, then GAE."""
+        TimeLimit bootstrap reward += gamma * V(terminal_obs) for truncated episodes, then GAE.
+        `replay`: dict(eps=(T,N,4), actions=(T,N,4)) of a recorded roll-out -- the head takes its noise from eps[t] instead of Philox
+        (vf_head_sample_eps: the same device function as vf_head_sample_at's) and keeps its own sample and log-prob in the buffer rows,
+        while the env is stepped with the recorded actions[t] -- how tests replay a recorded run of the reference's collect_rollouts
+        with the env held on the recorded trajectory (tests/test_ppo_loop_gpu.py).  Launch by launch: the persistent launch draws its
+        own noise."""
         env, buf = self.env, self.buf
+        if replay is not None:
+            as_dev = lambda a: th.as_tensor(a, dtype=th.float32).to(self.device).contiguous()
+            r_eps, r_act = as_dev(replay["eps"]), as_dev(replay["actions"])
+            if r_eps.shape != buf.actions.shape or r_act.shape != buf.actions.shape:
+                raise ValueError(f"collect_rollouts(replay=...): eps and actions must be {tuple(buf.actions.shape)}")
         if self._last_obs is None:
             self._last_obs = env.reset()
             self._last_starts = th.ones(self.n_envs, device=self.device)
@@ -1091,7 +1101,7 @@ class PPO:
         buf.episode_starts[0].copy_(self._last_starts)
         bs = self._bootstrap_list() if self.defer_bootstrap else None
         fused = False
-        if self.fused_rollout and self.defer_bootstrap and hasattr(env, "collect_policy"):
+        if replay is None and self.fused_rollout and self.defer_bootstrap and hasattr(env, "collect_policy"):
             # the whole loop below as one persistent launch (vf_ppo_rollout); same buffer rows, same Philox counters
             for k in self.obs_keys:
                 if k == "state":
@@ -1109,11 +1119,14 @@ class PPO:
             action, logp = buf.actions[t], buf.log_probs[t]
             mean, _ = pol.forward({k: obs[k] for k in self.obs_keys}, save_activations=False, out_value=buf.values[t])
             self._sample_step += 1
-            _lib.check(L.vf_head_sample_at(_ptr(mean), _ptr(pol.log_std), _ptr(action), _ptr(logp), N, self._row0, self._noise_key,
-                                           self._sample_step, 0, self._stream()))
+            if replay is None:
+                _lib.check(L.vf_head_sample_at(_ptr(mean), _ptr(pol.log_std), _ptr(action), _ptr(logp), N, self._row0, self._noise_key,
+                                               self._sample_step, 0, self._stream()))
+            else:
+                _lib.check(L.vf_head_sample_eps(_ptr(mean), _ptr(pol.log_std), _ptr(r_eps[t]), _ptr(action), _ptr(logp), N, self._stream()))
             for k in self.obs_keys:
                 buf.obs[k][t].copy_(obs[k])
-            obs, reward, done, _info = env.step(action)
+            obs, reward, done, _info = env.step(action if replay is None else r_act[t])
             if not self.defer_bootstrap:
                 _lib.check(L.vf_episode_stats(done.data_ptr(), _ptr(env._ep_return), _ptr(env._ep_length), _ptr(env._ep_flags),
                                               self._ep_stats.data_ptr(), N, self._stream()))
