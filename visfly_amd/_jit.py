@@ -56,6 +56,17 @@ PREBUILD_ACT = {
     "tanh_nav": ({"state": 13, "target": 3}, {"state": [128, 64], "target": [128, 64]}, [64, 64], [64, 64], (4, 1), (2, 1)),
     "tanh_hover": ({"state": 13}, {"state": [128, 64]}, [64, 64], [64, 64], (4, 1), (2, 1)),
     "elu_leaky_nav": ({"state": 13, "target": 3}, {"state": [128, 64], "target": [128, 64]}, [64, 64], [64, 64], (4, 1), (3, 4)),
+    # BPTT's two actors with a Tanh / ELU / LeakyReLU trunk (activation_fn; the extractor MLP keeps its default ReLU) on the sac_hover sizes:
+    # the SAC-style Actor (policy="MultiInputPolicy") and the one-head MlpPolicy actor, whose horizons step the policy-only class
+    "sac_hover_tanh": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 4), (2, 1)),
+    "sac_hover_elu": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 4), (3, 1)),
+    "sac_hover_leaky": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 4), (4, 1)),
+    "pi_hover_tanh": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 1), (2, 1)),
+    "pi_hover_elu": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 1), (3, 1)),
+    "pi_hover_leaky": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 1), (4, 1)),
+    # ... and on the reference's sizes: the actor of tests/golden/bptt_loop_hover_tanh.npz (the reference's own BPTT.learn with activation_fn=Tanh; its
+    # env replays recorded spawns, so its horizon steps launch by launch: the chain class alone)
+    "sac_loop_tanh": ({"state": 13}, {"state": [128, 64]}, [64, 64], [64, 64], (4, 4), (2, 1)),
 }
 # the twin critic (heads (1, 1) + pass-through action; td_policies.ContinuousCritic) on non-default shapes: (.., head_dims, passthrough)
 PREBUILD_CRITIC = {
@@ -69,9 +80,12 @@ PREBUILD_SAC = {
 }
 # ... and their roll-out plugins for the configurations tests/test_ppo_gpu.py runs: (shape name, (VF_ENV_*, VF_ACT_*, VF_INT_*, ctrl_delay))
 # ... and the BPTT plugins (both persistent launches of a horizon) tests/test_chain_jit_gpu.py runs: (shape name in PREBUILD_SAC / PREBUILD,
-# (kernel-side env kind, VF_ACT_*, VF_INT_*, ctrl_delay))
+# (kernel-side env kind, VF_ACT_*, VF_INT_*, ctrl_delay)); the names ending in an activation are PREBUILD_ACT's (tests/test_bptt_activations_gpu.py)
 PREBUILD_BPTT = [("sac_hover", (0, 1, 0, True)), ("sac_nav_bptt", (1, 1, 0, True)), ("one_layer_extractor", (0, 0, 0, True)),
-                 ("sac_hover", (3, 0, 0, True))]        # RacingEnv2: kernel-side kind VF_ENV_RACING2, thrust
+                 ("sac_hover", (3, 0, 0, True)),        # RacingEnv2: kernel-side kind VF_ENV_RACING2, thrust
+                 ("sac_hover_tanh", (0, 1, 0, True)), ("sac_hover_elu", (0, 1, 0, True)), ("sac_hover_leaky", (0, 1, 0, True)),
+                 ("pi_hover_tanh", (0, 1, 0, True)), ("pi_hover_elu", (0, 1, 0, True)), ("pi_hover_leaky", (0, 1, 0, True)),
+                 ("sac_hover_tanh", (2, 0, 0, True))]   # RacingEnv, thrust
 PREBUILD_ROLLOUT = [("verdict", (1, 1, 0, True)), ("one_layer_extractor", (0, 1, 1, False)), ("one_layer_extractor", (1, 1, 0, True)),
                     ("one_layer_extractor", (2, 1, 0, True)), ("one_layer_extractor", (3, 1, 0, True))]      # RacingEnv / RacingEnv2 (kernel-side kind 3)
 
@@ -330,13 +344,21 @@ def ensure_bptt(shape, cfg):
     return _loaded[key] is not None
 
 
+def prebuild_shape(name):
+    """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC, or of PREBUILD_ACT (with its activations)"""
+    if name in PREBUILD_ACT:
+        v = PREBUILD_ACT[name]
+        return shape_of(*v[:5], acts=v[5])
+    return shape_of(*{**PREBUILD, **PREBUILD_SAC}[name])
+
+
 def prebuild(verbose=False):
     """compile the PREBUILD shapes (in parallel) -> paths"""
     act = [shape_of(*v[:5], acts=v[5]) for v in PREBUILD_ACT.values()]
     jobs = ([(shape_of(*v), None) for v in list(PREBUILD.values()) + list(PREBUILD_SAC.values()) + list(PREBUILD_CRITIC.values())] +
             [(sh, None) for sh in act] +
             [(shape_of(*PREBUILD[n]), cfg) for n, cfg in PREBUILD_ROLLOUT] + [(act[0], (1, 1, 0, True))] +       # + the Tanh policy's roll-out on NavigationEnv
-            [(shape_of(*{**PREBUILD, **PREBUILD_SAC}[n]), ("bptt",) + cfg) for n, cfg in PREBUILD_BPTT])
+            [(prebuild_shape(n), ("bptt",) + cfg) for n, cfg in PREBUILD_BPTT])
     # every chain job runs four hipcc parts of fully unrolled kernels: bound the number in flight by the cores of the build box
     with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), (os.cpu_count() or 4) // 4))) as pool:
         paths = list(pool.map(lambda j: build(j[0], verbose, rollout=j[1]), jobs))

@@ -144,27 +144,41 @@ class BPTT:
             pk.setdefault("activation_fn", "relu")                    # MTDPolicy's default activation IS ReLU (td_policies.py:297)
         pk.setdefault("activation_fn", "relu")
         pk = checkpoint.policy_kwargs_from_reference(pk, self.obs_keys)
-        self._relu_only(pk)
+        act, ext_act = self._activations(pk)
         self._extractor = pk.get("extractor", {k: [128, 64] for k in self.obs_keys})
         self._ext_keys = list(self._extractor.keys())
         arch = list(pk.get("pi", [64, 64]))
         if self._critic_arch is None:
             self._critic_arch = list(arch)
         pol = MlpPolicy({k: obs[k].shape[1] for k in self.obs_keys}, self._extractor, arch, arch, self.device, seed=seed,
-                        ortho_init=False, head_dims=(4, 4), log_std_param=False)
+                        ortho_init=False, head_dims=(4, 4), log_std_param=False, activation=act, extractor_activation=ext_act)
         hidden = lambda trunk: [ly for ly in pol.layers if ly.dst.startswith(trunk + ":")]
         for a, b in zip(hidden("pi"), hidden("vf")):                  # log_latent_pi starts as a copy of latent_pi
             pol.weight(b).copy_(pol.weight(a))
             pol.bias(b).copy_(pol.bias(a))
         return pol
 
-    @staticmethod
-    def _relu_only(pk):
-        """BPTT / SHAC run their horizons on the persistent chain launches, which are ReLU networks (td_policies' own default,
-        td_policies.py:297); Tanh / ELU / LeakyReLU policies: PPO"""
+    # MTDPolicy takes any activation_fn (td_policies.py:297).  BPTT's two actors run ReLU, Tanh, ELU and LeakyReLU through every path of a
+    # horizon: the activation is part of the generated chain class (visfly_amd/_jit.py) and of the layer tables the block-tile / per-layer
+    # kernels read.  SHAC (its actor and its twin critic) still runs ReLU networks only
+    any_activation = True
+
+    def _activations(self, pk):
+        """(trunk, extractor) VF_ACTIVATION_* of translated policy_kwargs; refuses what this trainer does not run"""
         from .ppo import activation_kind
-        if (activation_kind(pk.get("activation", 1)), activation_kind(pk.get("extractor_activation", 1))) != (1, 1):
-            raise NotImplementedError("BPTT / SHAC: activation_fn other than relu is not implemented (the horizon kernels are ReLU networks)")
+        # (native MlpPolicy arguments pass through the translation untouched: there `activation` may be spelt `activation_fn`)
+        kinds = activation_kind(pk.get("activation", pk.get("activation_fn", 1))), activation_kind(pk.get("extractor_activation", 1))
+        if not self.any_activation:
+            self._relu_only(kinds)
+        return kinds
+
+    @staticmethod
+    def _relu_only(kinds):
+        """SHAC runs its horizons and its twin critic's update as ReLU networks (td_policies' own default, td_policies.py:297);
+        Tanh / ELU / LeakyReLU actors: BPTT, PPO"""
+        if tuple(kinds) != (1, 1):
+            raise NotImplementedError("SHAC: activation_fn other than relu is not implemented (SHAC's actor and twin critic run as ReLU "
+                                      "networks; BPTT and PPO take tanh / elu / leaky_relu)")
 
     def _head_fwd(self, mu, log_std, eps, action):
         """action = tanh(mu + eps exp(clamp(log_std))) -- Actor.action_log_prob's sample (SB3 squashed Gaussian)"""
@@ -179,12 +193,12 @@ class BPTT:
         pk = dict(policy_kwargs or {})
         pk.setdefault("activation_fn", "relu")             # (this actor is not a reference class: its default stays what it was)
         pk = checkpoint.policy_kwargs_from_reference(pk, self.obs_keys)
-        self._relu_only(pk)
+        act, ext_act = self._activations(pk)
         self.weight_decay = pk.get("weight_decay", self.weight_decay)
         return MlpPolicy({k: obs[k].shape[1] for k in self.obs_keys},
                          pk.get("extractor", {k: [128, 64] for k in self.obs_keys}), pk.get("pi", [64, 64]),
                          pk.get("vf", [64, 64]), self.device, log_std_init=pk.get("log_std_init", -1.0), seed=seed,
-                         ortho_init=pk.get("ortho_init", True))
+                         ortho_init=pk.get("ortho_init", True), activation=act, extractor_activation=ext_act)
 
     def _update(self):
         """one horizon: roll out, back-propagate through simulator and policy, clip + Adam (BPTT.py:100-134)"""
@@ -388,10 +402,11 @@ class BPTT:
                 "opt_step": int(self._opt_step), "num_timesteps": int(self.num_timesteps), "rng": self._gen.get_state().cpu(),
                 "noise_step": int(self._noise_step),
                 "spec": dict(extractor=self._extractor, pi=self.policy.spec["pi"], qf=self._critic_arch, horizon=self.H,
-                             gamma=self.gamma, learning_rate=self.lr, algo=type(self).__name__,
+                             gamma=self.gamma, learning_rate=self.lr, algo=type(self).__name__, **checkpoint.activation_spec(self.policy),
                              share_features_extractor=bool(getattr(self, "_share_extractor", False)))}
 
     def _load_state(self, d, load_optimizer=True):
+        checkpoint.check_activations(self.policy, d.get("spec"))
         assert d["actor"].numel() == self.policy.flat.numel(), "actor: the archive holds a different network (pass the same policy_kwargs, or use load())"
         self.policy.flat.copy_(d["actor"])
         self.policy.mark_updated()
@@ -417,8 +432,9 @@ class BPTT:
     def _policy_kwargs_from_spec(spec):
         """the stored network shapes as SB3-style policy_kwargs (what _make_reference_actor parses)"""
         return dict(features_extractor_class="StateTargetExtractor" if len(spec["extractor"]) > 1 else "StateExtractor",
-                    features_extractor_kwargs={"net_arch": {k: {"layer": list(v)} for k, v in spec["extractor"].items()}},
-                    net_arch=dict(pi=list(spec["pi"]), qf=list(spec["qf"])), activation_fn="relu",
+                    features_extractor_kwargs={"net_arch": {k: {"layer": list(v)} for k, v in spec["extractor"].items()},
+                                               "activation_fn": spec.get("extractor_activation", "relu")},
+                    net_arch=dict(pi=list(spec["pi"]), qf=list(spec["qf"])), activation_fn=spec.get("activation", "relu"),
                     share_features_extractor=bool(spec.get("share_features_extractor", False)))
 
     @classmethod

@@ -167,6 +167,26 @@ def _param_order(policy):
     return order
 
 
+def activation_spec(policy) -> dict:
+    """the (trunk, extractor) activations of a policy under the names MlpPolicy.spec uses, ReLU included"""
+    from .ppo import ACTIVATIONS
+    name = {v: k for k, v in ACTIVATIONS.items()}
+    return dict(activation=name[policy.act], extractor_activation=name[policy.ext_act])
+
+
+def check_activations(policy, spec):
+    """weights must never run through another nonlinearity than the one they were trained with: ValueError when the activations an
+    archive's spec names differ from the policy's.  A spec without the fields (archives written before they existed) is a ReLU network."""
+    from .ppo import activation_kind
+    spec = spec if isinstance(spec, dict) else {}
+    want = activation_kind(spec.get("activation", "relu")), activation_kind(spec.get("extractor_activation", "relu"))
+    if want != (policy.act, policy.ext_act):
+        have = activation_spec(policy)
+        raise ValueError(f"the archive holds a network with activations {spec.get('activation', 'relu')} (trunks) / "
+                         f"{spec.get('extractor_activation', 'relu')} (extractor), this trainer's policy has {have['activation']} / "
+                         f"{have['extractor_activation']}: pass the archive's activation_fn (or use load(), which reads it)")
+
+
 def _hyper(trainer) -> dict:
     keys = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef", "vf_coef", "max_grad_norm",
             "lr", "weight_decay", "adam_eps", "betas", "normalize_advantage", "target_kl", "seed", "H", "num_timesteps", "_opt_step",
@@ -175,7 +195,9 @@ def _hyper(trainer) -> dict:
     # schedules (callables of progress_remaining) are archived as their current value: an archive holds data, not code
     out = {k: (trainer._now(v) if callable(v) else v) for k, v in out.items()}
     out["learning_rate"] = out.pop("lr", None)
-    out["algorithm"], out["policy_spec"] = type(trainer).__name__, trainer.policy.spec
+    out["algorithm"], out["policy_spec"] = type(trainer).__name__, dict(trainer.policy.spec)
+    if hasattr(trainer, "any_activation"):       # BPTT / SHAC: the activations are always named (PPO's ReLU archives keep the r05 spec)
+        out["policy_spec"].update(activation_spec(trainer.policy))
     out["obs_dims"] = trainer.policy.obs_dims
     return out
 
@@ -254,6 +276,8 @@ def load_into(trainer, path: str, load_optimizer: bool = True):
     the Adam moments and step count"""
     sd, opt, data = read_archive(path)
     pol = trainer.policy
+    if hasattr(trainer, "any_activation") and isinstance(data, dict):      # BPTT / SHAC archives (see _hyper)
+        check_activations(pol, data.get("policy_spec"))
     load_policy_state_dict(pol, sd, strict=True)
     if load_optimizer and opt and opt.get("state"):
         order = _param_order(pol)

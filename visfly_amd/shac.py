@@ -104,6 +104,7 @@ class SHAC(BPTT):
     # the Actor (extractor -> latent_pi -> mu | log_latent_pi -> log_std) and its action head are BPTT's reference-actor path
     # (bptt.py::_make_reference_actor / _head_fwd): the reference's BPTT and SHAC share td_policies.Actor
     reference_actor = True
+    any_activation = False          # (BPTT._activations: SHAC's horizons and its twin critic are ReLU networks)
 
     def _q(self, net, obs, action, save=False, slot=0):
         q0, q1 = net.forward({**{k: obs[k] for k in self._ext_keys}, "action": action}, save_activations=save, slot=slot)
