@@ -787,3 +787,114 @@ void vfo_xmath(int kind, const float* a, const float* b, float* out, int64_t n)
         }
     }
 }
+
+/* ---------- the device random streams, restated (visfly_amd/csrc/vf_common.hpp, vf_env_device.hpp) ---------- */
+/* Philox4x32-10 (Salmon et al., SC'11): the 64-bit product split into hi and lo, 10 rounds, the key bumped after every round */
+static inline void philox_block(const uint32_t c[4], uint32_t k0, uint32_t k1, uint32_t o[4])
+{
+    uint32_t x = c[0], y = c[1], z = c[2], w = c[3];
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x, p1 = (uint64_t)0xCD9E8D57u * z;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        x = hi1 ^ y ^ k0; y = lo1; z = hi0 ^ w ^ k1; w = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o[0] = x; o[1] = y; o[2] = z; o[3] = w;
+}
+
+void vfo_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) philox_block(ctr + 4 * i, key[2 * i], key[2 * i + 1], out + 4 * i);
+}
+
+static inline float u01_24(uint32_t x) { return (float)(x & 0xFFFFFFu) * (1.0f / 16777216.0f); }
+
+/* sincos_spawn: one Cody-Waite reduction on pi/2 (split in two), minimax polynomials on [-pi/4, pi/4]; the fmaf sites are the device's */
+static inline void sincos_spawn(float x, float* sn, float* cs)
+{
+    const float k = rintf(x * 0.636619772367581343f);
+    float r = fmaf(k, -1.5707962512969971f, x);
+    r = fmaf(k, -7.5497894158615964e-8f, r);
+    const float z = r * r;
+    const float ps = fmaf(fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f) * z, r, r);
+    const float pc = fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f) * z, z,
+                          fmaf(-0.5f, z, 1.0f));
+    const int q = (int)k;
+    const float a = (q & 1) ? pc : ps, b = (q & 1) ? ps : pc;
+    *sn = (q & 2) ? -a : a;
+    *cs = ((q + 1) & 2) ? -b : b;
+}
+
+void vfo_sincos_spawn(const float* x, float* sn, float* cs, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) sincos_spawn(x[i], sn + i, cs + i);
+}
+
+void vfo_spawn(uint64_t seed, uint32_t agent0, const int32_t* agent, const uint32_t* episode, int n, int indexed,
+               const vfo_spawn_box* boxes, int n_boxes, float* state, float* t)
+{
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int j = 0; j < n; ++j) {
+        const uint32_t id = agent0 + (uint32_t)agent[j];
+        uint32_t r[12];
+        for (uint32_t blk = 0; blk < 3; ++blk) {
+            const uint32_t c[4] = {id, episode[j], blk, 0x5eedu};
+            philox_block(c, k0, k1, r + 4 * blk);
+        }
+        float u[12];
+        for (int m = 0; m < 12; ++m) u[m] = u01_24(r[m]);
+        /* the union pick and the indexed reset's t: the twelve top bytes the uniforms leave over */
+        const uint32_t pick = (r[0] >> 24) | ((r[1] >> 24) << 8) | ((r[2] >> 24) << 16) | ((r[3] >> 24) << 24);
+        const uint32_t tbits = (r[4] >> 24) | ((r[5] >> 24) << 8) | ((r[6] >> 24) << 16);
+        const vfo_spawn_box* sb = boxes + (n_boxes > 1 ? pick % (uint32_t)n_boxes : 0u);
+        float* s = state + 13 * (size_t)j;
+        float eul[3];
+        for (int d = 0; d < 3; ++d) {
+            s[d] = sb->pos_mean[d] + (2.0f * u[d] - 1.0f) * sb->pos_half[d];
+            eul[d] = (2.0f * u[3 + d] - 1.0f) * sb->ori_half[d] + sb->ori_mean[d];
+            s[7 + d] = (2.0f * u[6 + d] - 1.0f) * sb->vel_half[d] + sb->vel_mean[d];
+            s[10 + d] = (2.0f * u[9 + d] - 1.0f) * sb->omg_half[d] + sb->omg_mean[d];
+        }
+        float cy, sy, cp, sp, cr, sr;   /* zyx: eul = (roll, pitch, yaw) */
+        sincos_spawn(eul[2] * 0.5f, &sy, &cy);
+        sincos_spawn(eul[1] * 0.5f, &sp, &cp);
+        sincos_spawn(eul[0] * 0.5f, &sr, &cr);
+        s[3] = cr * cp * cy + sr * sp * sy;
+        s[4] = sr * cp * cy - cr * sp * sy;
+        s[5] = cr * sp * cy + sr * cp * sy;
+        s[6] = cr * cp * sy - sr * sp * cy;
+        t[j] = indexed ? u01_24(tbits) * 3.14f * 2.0f : 0.0f;
+    }
+}
+
+void vfo_spawn_drag(uint64_t seed, uint32_t agent0, const int32_t* agent, const uint32_t* episode, int n, float drag_random,
+                    const float* k_lin_mean, const float* k_quad_mean, float* k_lin, float* k_quad)
+{
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const float r2 = 2.0f * drag_random;
+    for (int j = 0; j < n; ++j) {
+        const uint32_t id = agent0 + (uint32_t)agent[j];
+        const uint32_t ca[4] = {id, episode[j], 4u, 0x5eedu}, cb[4] = {id, episode[j], 5u, 0x5eedu};
+        uint32_t a[4], b[4];
+        philox_block(ca, k0, k1, a);
+        philox_block(cb, k0, k1, b);
+        for (int d = 0; d < 3; ++d) {
+            k_lin[3 * (size_t)j + d] = k_lin_mean[d] * (clampf((u01_24(a[d]) - 0.5f) * r2, -0.5f, 0.5f) + 1.0f);
+            k_quad[3 * (size_t)j + d] = k_quad_mean[d] * (clampf((u01_24(b[d]) - 0.5f) * r2, -0.5f, 0.5f) + 1.0f);
+        }
+    }
+}
+
+void vfo_noise_uniforms(const uint32_t* row, const uint64_t* step, int64_t n, uint32_t tag, uint64_t seed, float* u)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t c[4] = {row[i], (uint32_t)step[i], (uint32_t)(step[i] >> 32), tag};
+        uint32_t r[4];
+        philox_block(c, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+        u[4 * i + 0] = ((float)(r[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+        u[4 * i + 1] = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
+        u[4 * i + 2] = ((float)(r[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+        u[4 * i + 3] = (float)(r[3] >> 8) * (1.0f / 16777216.0f);
+    }
+}
