@@ -1,4 +1,6 @@
-"""bench.py on another build of the library (A/B): VF_ALT_LIB=/path/lib.so python tools/bench_alt.py <bench.py arguments>"""
+"""bench.py on another build of the library (A/B): VF_ALT_LIB=/path/lib.so python tools/bench_alt.py <bench.py arguments>
+bench.py rebuilds a library that is older than the sources (from THIS tree): `touch` the other build first and check build.rebuilt = false
+in the JSON line (profiles/env_pair_algebra.txt, section 3)."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

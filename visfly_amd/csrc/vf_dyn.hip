@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kBlock) void k_dyn_step(const vf_dyn_cfg* __restric
 #pragma unroll
         for (int k = 0; k < 3; ++k) { kl[k] = c.k_lin[k]; kq[k] = c.k_quad[k]; }
     }
-    control_interval<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.vstrided != 0);
+    control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.vstrided != 0);
     store_agent(g.S, g.G, i, s, sp);
     if (g.obs) {
         float o[13];

@@ -13,16 +13,13 @@
 #include <hip/hip_runtime.h>
 
 #include "vf_common.hpp"
+#include "vf_pair_algebra.hpp"
 #include "vf_xmath.hpp"
 #include "visfly_amd.h"
 
 #pragma clang fp contract(off)
 
 namespace vf {
-
-struct Quat {
-    float w, x, y, z;
-};
 
 struct Agent {
     float p[3];
@@ -37,18 +34,7 @@ struct Agent {
     float wnd[3]; // wind velocity of this control interval: vf_dyn_cfg.wind, or the agent's row of vf_*_set_wind (not slab state)
 };
 
-// Hamilton product; term order and rounding of utils/maths.py:168-174
-__device__ __forceinline__ Quat qmul(const Quat& a, const Quat& b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x;
-    r.z = a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w;
-    return r;
-}
-
-__device__ __forceinline__ Quat qconj(const Quat& a) { return Quat{a.w, -a.x, -a.y, -a.z}; }
+// Quat, qmul, qconj, mat3, mat4 and their register-pair forms (QuatP, qmul_p, mat3_p, mat4_p): vf_pair_algebra.hpp
 
 // th.clamp: min(max(v, lo), hi) with NaN passing through
 __device__ __forceinline__ float clampf(float v, float lo, float hi)
@@ -57,31 +43,59 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi)
     return r > hi ? hi : r;
 }
 
-// (3x3) @ x as the k-ordered FMA chain of the reference's sgemm
-__device__ __forceinline__ void mat3(const float* __restrict__ A, float x0, float x1, float x2, float* o)
+// the rotor model's constants as rotors_p reads them: K0 = (c_motor, tm0), K1 = (tm1, tm2), in VGPRs
+struct RotorK {
+    vf_f2 K0, K1;
+};
+__device__ __forceinline__ RotorK rotor_k(const vf_dyn_cfg& c)
 {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float acc = A[3 * i] * x0;
-        acc = __builtin_fmaf(A[3 * i + 1], x1, acc);
-        acc = __builtin_fmaf(A[3 * i + 2], x2, acc);
-        o[i] = acc;
-    }
+    RotorK k{pair_of(c.c_motor, c.tm0), pair_of(c.tm1, c.tm2)};
+    keep_in_vgprs(k.K0);
+    keep_in_vgprs(k.K1);
+    return k;
 }
 
-__device__ __forceinline__ void mat4(const float* __restrict__ A, const float* x, float* o)
+// The wave-uniform matrices of the sub-steps as column pairs in VGPRs (vf_pair_algebra.hpp), arranged once per control interval.
+struct IntervalMats {
+    Mat4P B;
+    Mat3P J, Jinv;
+    RotorK k;
+};
+__device__ __forceinline__ IntervalMats interval_mats(const vf_dyn_cfg& c)
 {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float acc = A[4 * i] * x[0];
-        acc = __builtin_fmaf(A[4 * i + 1], x[1], acc);
-        acc = __builtin_fmaf(A[4 * i + 2], x[2], acc);
-        acc = __builtin_fmaf(A[4 * i + 3], x[3], acc);
-        o[i] = acc;
-    }
+    return IntervalMats{mat4_pairs(c.B), mat3_pairs(c.J), mat3_pairs(c.Jinv), rotor_k(c)};
 }
 
-// Integrator._get_derivatives for (q, omega)  (utils/maths.py:311,314)
+// a 3-vector as the mat3_p results come: component 0 by itself, (1, 2) as a pair
+struct Vec3P {
+    float x;
+    vf_f2 yz;
+};
+
+// Integrator._get_derivatives for (q, omega)  (utils/maths.py:311,314) on pairs: wq = (0, w) as a pure-vector quaternion,
+// (ft01, ft23) = [F, tau] as motor_substep leaves it (tau = ft01.hi, ft23.lo, ft23.hi)
+__device__ __forceinline__ void derivs(const IntervalMats& M, const QuatP& q, const QuatP& wq, const vf_f2 ft01, const vf_f2 ft23,
+                                       QuatP& dq, Vec3P& dw)
+{
+    const QuatP p = qmul_p<false, false>(q, wq);
+    const vf_f2 half = {0.5f, 0.5f};
+    dq.wx = p.wx * half;
+    dq.yz = p.yz * half;
+    float Jw0;
+    vf_f2 Jw12;
+    mat3_p(M.J, wq.wx, wq.yz, Jw0, Jw12);
+    const float w0 = wq.wx[1], w1 = wq.yz[0], w2 = wq.yz[1];
+    // torch.linalg.cross contracts to fma(a_i, b_j, -(a_j*b_i))
+    const float c0 = __builtin_fmaf(w1, Jw12[1], -(w2 * Jw12[0]));
+    const float c1 = __builtin_fmaf(w2, Jw0, -(w0 * Jw12[1]));
+    const float c2 = __builtin_fmaf(w0, Jw12[0], -(w1 * Jw0));
+    vf_f2 d0p = ft01;              // the low half is not read
+    d0p[1] = ft01[1] - c0;
+    const vf_f2 d12 = {ft23[0] - c1, ft23[1] - c2};
+    mat3_p(M.Jinv, d0p, d12, dw.x, dw.yz);
+}
+
+// ... on scalars (the persistent roll-out kernels and the adjoint kernels' replay keep the scalar forms)
 __device__ __forceinline__ void derivs(const vf_dyn_cfg& c, const Quat& q, const float* w, const float* tq,
                                        float* dq, float* dw)
 {
@@ -256,7 +270,20 @@ __device__ __forceinline__ void rotor_setpoint(const vf_dyn_cfg& c, const float*
     }
 }
 
-// _run_motors + allocation (:338-339,505-534): wm, T updated; ft = [F, tau]
+// _run_motors + allocation (:338-339,505-534): wm, T updated; (ft01, ft23) = [F, tau].  Rotors (0,1) and (2,3) as pairs.
+template <bool CTRL_DELAY>
+__device__ __forceinline__ void motor_substep(const RotorK& k, const Mat4P& B, const vf_f2* Td, const vf_f2* wd, vf_f2* wm, vf_f2* T,
+                                              vf_f2& ft01, vf_f2& ft23)
+{
+    if constexpr (CTRL_DELAY) {
+        rotors_p(B, k.K0, k.K1, wd, wm, T, ft01, ft23);               // :514, :530-534, :339
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) T[h] = Td[h];                     // :518
+        mat4_p(B, T[0], T[1], ft01, ft23);                             // :339
+    }
+}
+// ... on scalars
 template <bool CTRL_DELAY>
 __device__ __forceinline__ void motor_substep(const vf_dyn_cfg& c, const float* Td, const float* wd, float* wm, float* T,
                                               float* ft)
@@ -275,7 +302,7 @@ __device__ __forceinline__ void motor_substep(const vf_dyn_cfg& c, const float* 
     mat4(c.B, T, ft);                                                  // :339
 }
 
-// linear acceleration from the state at the START of the sub-step (:342-347)
+// linear acceleration from the state at the START of the sub-step (:342-347), scalar form
 __device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const Quat& q, const float* v, float F, const float* kl,
                                            const float* kq, float* acc)
 {
@@ -296,9 +323,29 @@ __device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const Quat& q, c
     acc[2] = ra.z / c.m + c.g_z;
 }
 
-// translation: acc, then p and v advance (maths.py:310,344,346 / repaired rk4 :353-386)
-template <int INTEG>
-__device__ __forceinline__ void trans_substep(const vf_dyn_cfg& c, const Quat& q, float F, const float* kl, const float* kq,
+// ... on pairs
+__device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const QuatP& q, const float* v, float F, const float* kl,
+                                           const float* kq, float* acc)
+{
+    const QuatP vq{pair_of(0.0f, v[0] + 0.0f), pair_of(v[1] + 0.0f, v[2] + 0.0f)};
+    const QuatP vb = qmul_p<false, false>(qmul_p<true, false>(q, vq), q);     // conj(q) * (0, v) * q
+    // drag and thrust in the body frame, component x by itself, (y, z) as a pair: u = (0, 0, 1) * F - (kl * vb + (kq * vb) * |vb|)
+    const vf_f2 kl12 = {kl[1], kl[2]}, kq12 = {kq[1], kq[2]}, e12 = {0.0f, 1.0f}, F2 = {F, F};
+    const vf_f2 ab12 = {__builtin_fabsf(vb.yz[0]), __builtin_fabsf(vb.yz[1])};
+    const vf_f2 zf12 = e12 * F2;
+    const float vbx = vb.wx[1];
+    const float ux = zf12[0] - (kl[0] * vbx + (kq[0] * vbx) * __builtin_fabsf(vbx));      // 0 * F, as for component y
+    const vf_f2 u12 = zf12 - (kl12 * vb.yz + (kq12 * vb.yz) * ab12);
+    const QuatP uq{pair_of(0.0f, ux), u12};
+    const QuatP ra = qmul_p<false, true>(qmul_p<false, false>(q, uq), q);     // q * (0, u) * conj(q)
+    acc[0] = ra.wx[1] / c.m + 0.0f;
+    acc[1] = ra.yz[0] / c.m + 0.0f;
+    acc[2] = ra.yz[1] / c.m + c.g_z;
+}
+
+// translation: acc, then p and v advance (maths.py:310,344,346 / repaired rk4 :353-386).  Q: Quat (scalar form) or QuatP (pairs)
+template <int INTEG, class Q>
+__device__ __forceinline__ void trans_substep(const vf_dyn_cfg& c, const Q& q, float F, const float* kl, const float* kq,
                                               const float* wind, float* p, float* v, float* acc)
 {
     linear_acc(c, q, v, F, kl, kq, acc);
@@ -332,7 +379,59 @@ __device__ __forceinline__ void trans_substep(const vf_dyn_cfg& c, const Quat& q
 
 // rotation: q and w advance, aa = angular acceleration handed to the controller, q re-normalised
 // (maths.py:311,314,345,347,351; dynamics.py:367; repaired rk4: SURVEY App. C-1 -- stages see the
-// caller's wind, ks-contractions are ((k1*w0 + k2*w1) + k3*w2) + k4*w3, tau stays frozen)
+// caller's wind, ks-contractions are ((k1*w0 + k2*w1) + k3*w2) + k4*w3, tau stays frozen).
+// On pairs: q = (w, x), (y, z); wq = (0, w) as a pure-vector quaternion (its zero is carried, never written)
+template <int INTEG>
+__device__ __forceinline__ void rot_substep(const vf_dyn_cfg& c, const IntervalMats& M, const vf_f2 ft01, const vf_f2 ft23, QuatP& q,
+                                            QuatP& wq, float* aa)
+{
+    const float dt = c.dt;
+    const vf_f2 dt2 = {dt, dt};
+    if constexpr (INTEG == VF_INT_EULER) {
+        QuatP dq;
+        Vec3P dw;
+        derivs(M, q, wq, ft01, ft23, dq, dw);
+        q.wx = q.wx + dq.wx * dt2;
+        q.yz = q.yz + dq.yz * dt2;
+        wq.wx[1] = wq.wx[1] + dw.x * dt;
+        wq.yz = wq.yz + dw.yz * dt2;
+        aa[0] = dw.x; aa[1] = dw.yz[0]; aa[2] = dw.yz[1];
+    } else {
+        const float ks0 = 1.0f / 6.0f, ks1 = 2.0f / 6.0f;
+        QuatP qc = q, wc = wq, dq, sq;
+        Vec3P dw, sw;
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            if (st != 0) {
+                const float h = st == 3 ? 1.0f : 0.5f;
+                const vf_f2 h2 = {h, h};
+                qc.wx = q.wx + dq.wx * h2 * dt2;
+                qc.yz = q.yz + dq.yz * h2 * dt2;
+                wc.wx[1] = wq.wx[1] + dw.x * h * dt;
+                wc.yz = wq.yz + dw.yz * h2 * dt2;
+            }
+            derivs(M, qc, wc, ft01, ft23, dq, dw);
+            const float ks = (st == 0 || st == 3) ? ks0 : ks1;
+            const vf_f2 ks2 = {ks, ks};
+            const Vec3P kw{dw.x * ks, dw.yz * ks2};
+            sw.x = st == 0 ? kw.x : sw.x + kw.x;
+            sw.yz = st == 0 ? kw.yz : sw.yz + kw.yz;
+            const QuatP kq4{dq.wx * ks2, dq.yz * ks2};
+            sq.wx = st == 0 ? kq4.wx : sq.wx + kq4.wx;
+            sq.yz = st == 0 ? kq4.yz : sq.yz + kq4.yz;
+        }
+        q.wx = q.wx + sq.wx * dt2;
+        q.yz = q.yz + sq.yz * dt2;
+        wq.wx[1] = wq.wx[1] + sw.x * dt;
+        wq.yz = wq.yz + sw.yz * dt2;
+        aa[0] = sw.x; aa[1] = sw.yz[0]; aa[2] = sw.yz[1];
+    }
+    const vf_f2 s01 = q.wx * q.wx, s23 = q.yz * q.yz;
+    const float nn = sqrtf(((s01[0] + s01[1]) + s23[0]) + s23[1]);   // :367, maths.py:226-230
+    q.wx = pair_of(q.wx[0] / nn, q.wx[1] / nn);
+    q.yz = pair_of(q.yz[0] / nn, q.yz[1] / nn);
+}
+// ... on scalars, tq = tau
 template <int INTEG>
 __device__ __forceinline__ void rot_substep(const vf_dyn_cfg& c, const float* tq, Quat& q, float* w, float* aa)
 {
@@ -416,6 +515,29 @@ struct NoCheckpoint {
     __device__ __forceinline__ void end(const Agent&) const {}
 };
 
+// rotor speeds, thrusts and set-points of the loop as pairs (0,1), (2,3)
+struct RotorsP {
+    vf_f2 Td[2], wd[2], wm[2], T[2];
+    __device__ __forceinline__ RotorsP(const Agent& s, const float* Td_, const float* wd_)
+    {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            Td[h] = pair_of(Td_[2 * h], Td_[2 * h + 1]);
+            wd[h] = pair_of(wd_[2 * h], wd_[2 * h + 1]);     // not read without ctrl_delay
+            wm[h] = pair_of(s.wm[2 * h], s.wm[2 * h + 1]);
+            T[h] = pair_of(s.T[2 * h], s.T[2 * h + 1]);
+        }
+    }
+    __device__ __forceinline__ void store(Agent& s) const
+    {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            s.wm[2 * h] = wm[h][0]; s.wm[2 * h + 1] = wm[h][1];
+            s.T[2 * h] = T[h][0]; s.T[2 * h + 1] = T[h][1];
+        }
+    }
+};
+
 // All sub-steps of one control interval in ONE thread (dynamics.py:335-382).  kl/kq: this agent's drag.
 template <int ACT, int INTEG, bool CTRL_DELAY, class CK = NoCheckpoint>
 __device__ __forceinline__ void control_interval(const vf_dyn_cfg& c, Agent& s, const float* a,
@@ -432,6 +554,40 @@ __device__ __forceinline__ void control_interval(const vf_dyn_cfg& c, Agent& s, 
         trans_substep<INTEG>(c, s.q, ft[0], kl, kq, s.wnd, s.p, s.v, s.acc);   // uses q of the sub-step start
         rot_substep<INTEG>(c, ft + 1, s.q, s.w, s.aa);
     }
+    ck.end(s);
+    finish_interval(c, s);
+}
+
+// control_interval with the sub-step loop on register pairs (vf_pair_algebra.hpp): the single-step kernels of vf_env.hip / vf_dyn.hip.
+// Bit-identical to control_interval (same IEEE operations in the same order).
+template <int ACT, int INTEG, bool CTRL_DELAY, class CK = NoCheckpoint>
+__device__ __forceinline__ void control_interval_pairs(const vf_dyn_cfg& c, Agent& s, const float* a,
+                                                 const float* kl, const float* kq, bool vstrided = false, const CK& ck = CK{})
+{
+    float Td[4], wd[4];
+    desired_thrusts<ACT>(c, s, a, Td, vstrided);
+    rotor_setpoint<CTRL_DELAY>(c, Td, wd);
+    // the rotational state and the rotors live on register pairs through the loop (vf_pair_algebra.hpp), converted before and after it
+    const IntervalMats M = interval_mats(c);
+    RotorsP r(s, Td, wd);
+    QuatP q = to_pairs(s.q), wq{pair_of(0.0f, s.w[0]), pair_of(s.w[1], s.w[2])};
+    const auto mirror = [&] {
+        r.store(s);
+        s.q = to_quat(q);
+        s.w[0] = wq.wx[1]; s.w[1] = wq.yz[0]; s.w[2] = wq.yz[1];
+    };
+#pragma unroll 1
+    for (int sub = 0; sub < c.interval_steps; ++sub) {
+        if constexpr (!__is_same(CK, NoCheckpoint)) {   // an observer reads the agent at the head of the sub-step
+            if (sub != 0) mirror();
+            ck.head(sub, s);
+        }
+        vf_f2 ft01, ft23;
+        motor_substep<CTRL_DELAY>(M.k, M.B, r.Td, r.wd, r.wm, r.T, ft01, ft23);
+        trans_substep<INTEG>(c, q, ft01[0], kl, kq, s.wnd, s.p, s.v, s.acc);   // uses q of the sub-step start
+        rot_substep<INTEG>(c, M, ft01, ft23, q, wq, s.aa);
+    }
+    mirror();
     ck.end(s);
     finish_interval(c, s);
 }
@@ -684,14 +840,20 @@ __device__ __forceinline__ void split_rotation_wave(const vf_dyn_cfg& c, const D
     float Td[4], wd[4];
     desired_thrusts<ACT>(c, s, a, Td);
     rotor_setpoint<CTRL_DELAY>(c, Td, wd);
+    const IntervalMats M = interval_mats(c);
+    RotorsP r(s, Td, wd);
+    QuatP q = to_pairs(s.q), wq{pair_of(0.0f, s.w[0]), pair_of(s.w[1], s.w[2])};
     for (int sub = 0; sub < c.interval_steps; ++sub) {
-        float ft[4];
-        motor_substep<CTRL_DELAY>(c, Td, wd, s.wm, s.T, ft);
+        vf_f2 ft01, ft23;
+        motor_substep<CTRL_DELAY>(M.k, M.B, r.Td, r.wd, r.wm, r.T, ft01, ft23);
         float(*x)[64] = sh.xq[sub & 1];
-        x[0][l] = s.q.w; x[1][l] = s.q.x; x[2][l] = s.q.y; x[3][l] = s.q.z; x[4][l] = ft[0];
+        x[0][l] = q.wx[0]; x[1][l] = q.wx[1]; x[2][l] = q.yz[0]; x[3][l] = q.yz[1]; x[4][l] = ft01[0];
         lds_publish_barrier();
-        rot_substep<INTEG>(c, ft + 1, s.q, s.w, s.aa);
+        rot_substep<INTEG>(c, M, ft01, ft23, q, wq, s.aa);
     }
+    r.store(s);
+    s.q = to_quat(q);
+    s.w[0] = wq.wx[1]; s.w[1] = wq.yz[0]; s.w[2] = wq.yz[1];
     float(*f)[64] = sh.fin;
     f[0][l] = s.q.w; f[1][l] = s.q.x; f[2][l] = s.q.y; f[3][l] = s.q.z;
 #pragma unroll
@@ -727,7 +889,7 @@ __device__ __forceinline__ void split_translation_wave(const vf_dyn_cfg& c, cons
     for (int sub = 0; sub < c.interval_steps; ++sub) {
         __builtin_amdgcn_s_barrier();
         const float(*x)[64] = sh.xq[sub & 1];
-        const Quat q{x[0][l], x[1][l], x[2][l], x[3][l]};
+        const QuatP q{pair_of(x[0][l], x[1][l]), pair_of(x[2][l], x[3][l])};
         const float F = x[4][l];
         trans_substep<INTEG>(c, q, F, kl, kq, s.wnd, s.p, s.v, s.acc);
     }

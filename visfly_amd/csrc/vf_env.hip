@@ -104,11 +104,11 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
         }
         __device__ __forceinline__ void end(const Agent&) const {}
     };
-    control_interval<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0, TraceCk{tr});
+    control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0, TraceCk{tr});
     asm volatile("" :: "v"(s.p[0]), "v"(s.q.w), "v"(s.v[0]), "v"(s.w[0]) : "memory");
     VF_TR(7);                                        // interval done
 #else
-    control_interval<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
+    control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
 #endif
     const int wave = threadIdx.x >> 6;
 #ifdef VF_ENV_TRACE
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void k_env_rollout(const vf_dyn_cfg* __rest
         if (c.delay_steps > 0) sp.vel = head_bits;
         float kl[3], kq[3];
         drag_of(c, g.d, i, kl, kq);
-        control_interval<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
+        control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
         env_epilogue<KIND, false>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
         if (++k >= g.K) break;
         g.d.action += g.action_stride;            // float4 units

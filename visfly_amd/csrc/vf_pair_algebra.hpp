@@ -1,0 +1,287 @@
+// Quaternion and small-matrix algebra of the sub-step loop, in scalar form and on register PAIRS (gfx950).
+//
+// A lone wave issues one VALU instruction per ~4 cycles whatever it is, and a v_pk_*_f32 instruction does two IEEE fp32 operations in
+// that slot (profiles/r02_valu_cost_probe.txt), so the sub-step loop pays per instruction, not per operation.  The pair layout keeps a
+// quaternion as two 64-bit register pairs (w, x) and (y, z); the Hamilton product on it is ONE asm statement of 8 packed multiplies and
+// 6 packed adds whose swaps and sign flips ride on op_sel / op_sel_hi / neg_lo / neg_hi.  The constant matrices are applied two rows at a
+// time from column pairs (A[r][k], A[r+1][k]) arranged once per control interval.
+//
+// Same products, same additions, same order as the scalar forms (utils/maths.py:168-174; the k-ordered FMA chains of the reference's
+// sgemm).  The only rewrites are (-a) * b for -(a * b) and x + (-y) for x - y, both exact in IEEE arithmetic, signed zeros included;
+// a pure-vector operand (0, v) keeps its zero and every term.  Each pair operation has a plain C++ body of the same operation order for
+// the host (tests/test_pair_algebra_host.py compiles both forms with the system compiler and compares them bit for bit).
+//
+// Self-contained: no HIP header needed, so that the host test can include it.  Compile with -ffp-contract=off.
+#pragma once
+
+#if defined(__HIPCC__)
+#define VF_PA_FN __device__ __forceinline__
+#else
+#define VF_PA_FN static inline
+#endif
+
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+namespace vf {
+
+struct Quat {
+    float w, x, y, z;
+};
+
+typedef float vf_f2 __attribute__((vector_size(8)));
+
+// (w, x) and (y, z)
+struct QuatP {
+    vf_f2 wx, yz;
+};
+
+VF_PA_FN vf_f2 pair_of(float lo, float hi)
+{
+    vf_f2 r = {lo, hi};
+    return r;
+}
+VF_PA_FN QuatP to_pairs(const Quat& a) { return QuatP{pair_of(a.w, a.x), pair_of(a.y, a.z)}; }
+VF_PA_FN Quat to_quat(const QuatP& a) { return Quat{a.wx[0], a.wx[1], a.yz[0], a.yz[1]}; }
+
+// Hamilton product; term order and rounding of utils/maths.py:168-174
+VF_PA_FN Quat qmul(const Quat& a, const Quat& b)
+{
+    Quat r;
+    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
+    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
+    r.y = a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x;
+    r.z = a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w;
+    return r;
+}
+
+VF_PA_FN Quat qconj(const Quat& a) { return Quat{a.w, -a.x, -a.y, -a.z}; }
+
+// (3x3) @ x as the k-ordered FMA chain of the reference's sgemm
+VF_PA_FN void mat3(const float* __restrict__ A, float x0, float x1, float x2, float* o)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float acc = A[3 * i] * x0;
+        acc = __builtin_fmaf(A[3 * i + 1], x1, acc);
+        acc = __builtin_fmaf(A[3 * i + 2], x2, acc);
+        o[i] = acc;
+    }
+}
+
+VF_PA_FN void mat4(const float* __restrict__ A, const float* x, float* o)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float acc = A[4 * i] * x[0];
+        acc = __builtin_fmaf(A[4 * i + 1], x[1], acc);
+        acc = __builtin_fmaf(A[4 * i + 2], x[2], acc);
+        acc = __builtin_fmaf(A[4 * i + 3], x[3], acc);
+        o[i] = acc;
+    }
+}
+
+// ---- the pair forms ------------------------------------------------------------------------------------------------------------------
+// qmul_p<CA, CB>(a, b) = qmul(CA ? qconj(a) : a, CB ? qconj(b) : b): the conjugate's sign flips are source modifiers of the multiplies
+// (the scalar form flips the sign bit first and multiplies then: the same product).  At most one of CA, CB.
+//
+// The eight packed multiplies (src0 = a pair of a, src1 = a pair of b; [lo,lo]*[lo,hi] and [hi,hi]*[hi,lo] selections):
+//   t0 = (aw bw, aw bx)  t1 = (ax bx, ax bw)  t2 = (ay by, ay bz)  t3 = (az bz, az by)        -> (r.w, r.x) = ((t0 -+ t1) -+ t2) -- t3
+//   u0 = (aw by, aw bz)  u1 = (ax bz, ax by)  u2 = (ay bw, ay bx)  u3 = (az bx, az bw)        -> (r.y, r.z) = ((u0 -+ u1) +- u2) ++ u3
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VF_PA_LL " op_sel:[0,0] op_sel_hi:[0,1]"   // (s0.lo * s1.lo, s0.lo * s1.hi)
+#define VF_PA_HH " op_sel:[1,1] op_sel_hi:[1,0]"   // (s0.hi * s1.hi, s0.hi * s1.lo)
+// N0 .. N7: the neg_lo / neg_hi text of the multiplies t0, u0, t1, u1, t2, u2, t3, u3
+#define VF_PA_QMUL(N0, N1, N2, N3, N4, N5, N6, N7)                                                                                  \
+    "v_pk_mul_f32 %0, %8, %10" VF_PA_LL N0 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %1, %8, %11" VF_PA_LL N1 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %2, %8, %10" VF_PA_HH N2 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %3, %8, %11" VF_PA_HH N3 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %4, %9, %11" VF_PA_LL N4 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %5, %9, %10" VF_PA_LL N5 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %6, %9, %11" VF_PA_HH N6 "\n\t"                                                                                  \
+    "v_pk_mul_f32 %7, %9, %10" VF_PA_HH N7 "\n\t"                                                                                  \
+    "v_pk_add_f32 %0, %0, %2 neg_lo:[0,1]\n\t"                                                                                     \
+    "v_pk_add_f32 %1, %1, %3 neg_lo:[0,1]\n\t"                                                                                     \
+    "v_pk_add_f32 %0, %0, %4 neg_lo:[0,1]\n\t"                                                                                     \
+    "v_pk_add_f32 %1, %1, %5 neg_hi:[0,1]\n\t"                                                                                     \
+    "v_pk_add_f32 %0, %0, %6 neg_lo:[0,1] neg_hi:[0,1]\n\t"                                                                        \
+    "v_pk_add_f32 %1, %1, %7"
+#define VF_PA_NA " neg_lo:[1,0] neg_hi:[1,0]"    // src0 negated in both halves
+#define VF_PA_NB " neg_lo:[0,1] neg_hi:[0,1]"    // src1 negated in both halves
+#define VF_PA_NBL " neg_lo:[0,1]"                // src1 negated where the low result reads it
+#define VF_PA_NBH " neg_hi:[0,1]"                // ... the high result
+#endif
+
+template <bool CA, bool CB>
+VF_PA_FN QuatP qmul_p(const QuatP& a, const QuatP& b)
+{
+    static_assert(!(CA && CB), "at most one conjugated operand");
+    QuatP r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    vf_f2 t1, u1, t2, u2, t3, u3;
+#define VF_PA_OPERANDS : "=&v"(r.wx), "=&v"(r.yz), "=&v"(t1), "=&v"(u1), "=&v"(t2), "=&v"(u2), "=&v"(t3), "=&v"(u3) \
+                       : "v"(a.wx), "v"(a.yz), "v"(b.wx), "v"(b.yz)
+    if constexpr (CA)         // a = (aw, -ax, -ay, -az): every multiply that reads ax, ay or az
+        asm(VF_PA_QMUL("", "", VF_PA_NA, VF_PA_NA, VF_PA_NA, VF_PA_NA, VF_PA_NA, VF_PA_NA) VF_PA_OPERANDS);
+    else if constexpr (CB)    // b = (bw, -bx, -by, -bz): the halves that read bx, by or bz
+        asm(VF_PA_QMUL(VF_PA_NBH, VF_PA_NB, VF_PA_NBL, VF_PA_NB, VF_PA_NB, VF_PA_NBH, VF_PA_NB, VF_PA_NBL) VF_PA_OPERANDS);
+    else
+        asm(VF_PA_QMUL("", "", "", "", "", "", "", "") VF_PA_OPERANDS);
+#undef VF_PA_OPERANDS
+#else
+    const float aw = a.wx[0], ax = CA ? -a.wx[1] : a.wx[1], ay = CA ? -a.yz[0] : a.yz[0], az = CA ? -a.yz[1] : a.yz[1];
+    const float bw = b.wx[0], bx = CB ? -b.wx[1] : b.wx[1], by = CB ? -b.yz[0] : b.yz[0], bz = CB ? -b.yz[1] : b.yz[1];
+    const vf_f2 t0 = {aw * bw, aw * bx}, u0 = {aw * by, aw * bz};
+    const vf_f2 t1 = {ax * bx, ax * bw}, u1 = {ax * bz, ax * by};
+    const vf_f2 t2 = {ay * by, ay * bz}, u2 = {ay * bw, ay * bx};
+    const vf_f2 t3 = {az * bz, az * by}, u3 = {az * bx, az * bw};
+    r.wx = pair_of(((t0[0] + -t1[0]) + -t2[0]) + -t3[0], ((t0[1] + t1[1]) + t2[1]) + -t3[1]);
+    r.yz = pair_of(((u0[0] + -u1[0]) + u2[0]) + u3[0], ((u0[1] + u1[1]) + -u2[1]) + u3[1]);
+#endif
+    return r;
+}
+
+// column pairs of a row-major 4x4 matrix: c01[k] = (A[0][k], A[1][k]), c23[k] = (A[2][k], A[3][k])
+struct Mat4P {
+    vf_f2 c01[4], c23[4];
+};
+// ... of a 3x3 one: row 0 by itself, c12[k] = (A[1][k], A[2][k]) -- the layout of a pure-vector quaternion (0, x0), (x1, x2)
+struct Mat3P {
+    float r0[3];
+    vf_f2 c12[3];
+};
+
+// A wave-uniform matrix arrives in SGPRs, and left to itself hipcc re-copies every pair into VGPRs where it is used (inside the loop):
+// the empty asm makes the VGPR pair the value's only home.
+VF_PA_FN void keep_in_vgprs(vf_f2& v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(v));
+#else
+    (void)v;
+#endif
+}
+
+VF_PA_FN Mat4P mat4_pairs(const float* __restrict__ A)
+{
+    Mat4P m;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m.c01[k] = pair_of(A[k], A[4 + k]);
+        m.c23[k] = pair_of(A[8 + k], A[12 + k]);
+        keep_in_vgprs(m.c01[k]);
+        keep_in_vgprs(m.c23[k]);
+    }
+    return m;
+}
+VF_PA_FN Mat3P mat3_pairs(const float* __restrict__ A)
+{
+    Mat3P m;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        m.r0[k] = A[k];
+        m.c12[k] = pair_of(A[3 + k], A[6 + k]);
+        keep_in_vgprs(m.c12[k]);
+    }
+    return m;
+}
+
+// mat4 on rows (0,1) and (2,3): every row keeps its chain fma(A[i][3], x3, fma(A[i][2], x2, fma(A[i][1], x1, A[i][0] * x0)))
+VF_PA_FN void mat4_p(const Mat4P& A, const vf_f2 x01, const vf_f2 x23, vf_f2& o01, vf_f2& o23)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_pk_mul_f32 %0, %2, %10 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+        "v_pk_mul_f32 %1, %6, %10 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+        "v_pk_fma_f32 %0, %3, %10, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %1, %7, %10, %1 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %0, %4, %11, %0 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %1, %8, %11, %1 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %0, %5, %11, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %1, %9, %11, %1 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+        : "=&v"(o01), "=&v"(o23)
+        : "v"(A.c01[0]), "v"(A.c01[1]), "v"(A.c01[2]), "v"(A.c01[3]), "v"(A.c23[0]), "v"(A.c23[1]), "v"(A.c23[2]), "v"(A.c23[3]),
+          "v"(x01), "v"(x23));
+#else
+    const float x[4] = {x01[0], x01[1], x23[0], x23[1]};
+    vf_f2 a = {A.c01[0][0] * x[0], A.c01[0][1] * x[0]}, b = {A.c23[0][0] * x[0], A.c23[0][1] * x[0]};
+    for (int k = 1; k < 4; ++k) {
+        a = pair_of(__builtin_fmaf(A.c01[k][0], x[k], a[0]), __builtin_fmaf(A.c01[k][1], x[k], a[1]));
+        b = pair_of(__builtin_fmaf(A.c23[k][0], x[k], b[0]), __builtin_fmaf(A.c23[k][1], x[k], b[1]));
+    }
+    o01 = a;
+    o23 = b;
+#endif
+}
+
+// The rotor recurrence and the allocation of one sub-step in ONE statement (dynamics.py:514,530-534,339), rotors (0,1) and (2,3) as pairs:
+//   wm = c_motor * wm + wd;  T = (tm0 * ((wm + 0) * (wm + 0)) + tm1 * wm) + tm2;  (ft01, ft23) = B @ T
+// K0 = (c_motor, tm0), K1 = (tm1, tm2).  The two pairs' chains alternate, so that no packed instruction reads the result of the one
+// before it (hipcc schedules the chains one after the other and pads every such pair with an s_nop).
+VF_PA_FN void rotors_p(const Mat4P& B, const vf_f2 K0, const vf_f2 K1, const vf_f2* wd, vf_f2* wm, vf_f2* T, vf_f2& ft01, vf_f2& ft23)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    vf_f2 a0, a1;
+    asm("v_pk_mul_f32 %0, %0, %8 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+        "v_pk_mul_f32 %1, %1, %8 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+        "v_pk_add_f32 %0, %0, %10\n\t"
+        "v_pk_add_f32 %1, %1, %11\n\t"
+        "v_pk_add_f32 %4, %0, 0 op_sel_hi:[1,0]\n\t"
+        "v_pk_add_f32 %5, %1, 0 op_sel_hi:[1,0]\n\t"
+        "v_pk_mul_f32 %4, %4, %4\n\t"
+        "v_pk_mul_f32 %5, %5, %5\n\t"
+        "v_pk_mul_f32 %4, %8, %4 op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_mul_f32 %5, %8, %5 op_sel:[1,0] op_sel_hi:[1,1]\n\t"
+        "v_pk_mul_f32 %2, %9, %0 op_sel:[0,0] op_sel_hi:[0,1]\n\t"
+        "v_pk_mul_f32 %3, %9, %1 op_sel:[0,0] op_sel_hi:[0,1]\n\t"
+        "v_pk_add_f32 %2, %4, %2\n\t"
+        "v_pk_add_f32 %3, %5, %3\n\t"
+        "v_pk_add_f32 %2, %2, %9 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_add_f32 %3, %3, %9 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_mul_f32 %6, %12, %2 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+        "v_pk_mul_f32 %7, %16, %2 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+        "v_pk_fma_f32 %6, %13, %2, %6 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %7, %17, %2, %7 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %6, %14, %3, %6 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %7, %18, %3, %7 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %6, %15, %3, %6 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+        "v_pk_fma_f32 %7, %19, %3, %7 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+        : "+v"(wm[0]), "+v"(wm[1]), "=&v"(T[0]), "=&v"(T[1]), "=&v"(a0), "=&v"(a1), "=&v"(ft01), "=&v"(ft23)
+        : "v"(K0), "v"(K1), "v"(wd[0]), "v"(wd[1]), "v"(B.c01[0]), "v"(B.c01[1]), "v"(B.c01[2]), "v"(B.c01[3]), "v"(B.c23[0]),
+          "v"(B.c23[1]), "v"(B.c23[2]), "v"(B.c23[3]));
+#else
+    for (int h = 0; h < 2; ++h)
+        for (int k = 0; k < 2; ++k) {
+            wm[h][k] = K0[0] * wm[h][k] + wd[h][k];
+            const float wp = wm[h][k] + 0.0f;
+            T[h][k] = (K0[1] * (wp * wp) + K1[0] * wm[h][k]) + K1[1];
+        }
+    mat4_p(B, T[0], T[1], ft01, ft23);
+#endif
+}
+
+// mat3 on a vector in the pure-vector layout x = (x0p.hi, x12.lo, x12.hi) (x0p.lo is not read): row 0 by itself, rows (1,2) as a pair;
+// every row keeps its chain fma(A[i][2], x2, fma(A[i][1], x1, A[i][0] * x0))
+// The three packed instructions read each other's result back to back, with no wait state.  Believed to need none, by this reasoning: a
+// VALU result read by the next VALU instruction is interlocked by the hardware, and the s_nop hipcc puts between such a pair in its own
+// code follows op_sel_hi[0] of the writer (it leaves v_pk_mul ... op_sel_hi:[0,1] -> v_pk_add unpadded), i.e. LLVM's rule for writes of a
+// register HALF, whose flag bit coincides with src0's op_sel_hi in this encoding; no v_pk_*_f32 writes a half.  Every fixture is 0 ulp
+// with it.  One observation is unexplained and should be ruled out against this before the reasoning is leaned on elsewhere: the
+// persistent PPO roll-out on the pair path did not reproduce the per-step loop (profiles/env_pair_algebra.txt, section 7).
+VF_PA_FN void mat3_p(const Mat3P& A, const vf_f2 x0p, const vf_f2 x12, float& o0, vf_f2& o12)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_pk_mul_f32 %0, %1, %4 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+        "v_pk_fma_f32 %0, %2, %5, %0 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %0, %3, %5, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+        : "=&v"(o12)
+        : "v"(A.c12[0]), "v"(A.c12[1]), "v"(A.c12[2]), "v"(x0p), "v"(x12));
+#else
+    o12 = pair_of(__builtin_fmaf(A.c12[2][0], x12[1], __builtin_fmaf(A.c12[1][0], x12[0], A.c12[0][0] * x0p[1])),
+                  __builtin_fmaf(A.c12[2][1], x12[1], __builtin_fmaf(A.c12[1][1], x12[0], A.c12[0][1] * x0p[1])));
+#endif
+    o0 = __builtin_fmaf(A.r0[2], x12[1], __builtin_fmaf(A.r0[1], x12[0], A.r0[0] * x0p[1]));
+}
+
+}  // namespace vf
