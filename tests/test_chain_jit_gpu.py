@@ -11,6 +11,8 @@ import warnings
 import pytest
 import torch
 
+from _gradcheck import assert_blocks, assert_blocks_agree, assert_rows, pinned_reference
+
 DEV = "cuda:0"
 from visfly_amd._jit import PREBUILD as SHAPES      # name -> (observation widths, extractor layers, pi, vf); __graft_entry__.build() compiles them
 
@@ -157,6 +159,8 @@ def test_generated_backward_vs_torch_and_block_tile_kernel(name, mode, M):
             if prm.grad is None:
                 prm.grad = torch.zeros_like(prm)
     gref = ref.flat_grad().to(DEV)
+    pol.forward(obs)
+    pin = pinned_reference(pol, obs, pol._buffers(M, 0), d_mean, d_value, ig, second_head=d_value is not None)
     res = {}
     for fused in (True, False, True):
         pol.fused_backward = fused
@@ -175,6 +179,10 @@ def test_generated_backward_vs_torch_and_block_tile_kernel(name, mode, M):
         assert (gk - gref).abs().max().item() <= 5e-6 * scale, (fused, (gk - gref).abs().max().item(), scale)
         for k, v in res[fused][1].items():
             assert torch.allclose(v, xs[k].grad, rtol=1e-4, atol=1e-6 * xs[k].grad.abs().max().item())
+        # ... and every block / every row on its own scale against the fp64 network (tests/_gradcheck.py)
+        assert_blocks(pol, res[fused][0], pin, f"generated {name} {mode} M={M} fused_backward={fused}")
+        for k, v in res[fused][1].items():
+            assert_rows(v, pin.d_in[k], pin.d_in32[k], f"generated {name} {mode} M={M} fused_backward={fused} {k}")
     pol.fused_backward = True
     pol.forward(obs)
     pol.backward(d_mean, d_value, None, accumulate=True, need_input_grad=ig)
@@ -215,12 +223,17 @@ def test_generated_fused_ppo_update_equals_separate_launches(name, B):
                                        adv.data_ptr(), ret.data_ptr(), d_mean.data_ptr(), d_value.data_ptr(), stats.data_ptr(), B,
                                        C.byref(cfg), scratch.data_ptr(), st))
             pol.backward(d_mean, d_value, None)
+            pin = pinned_reference(pol, obs, pol._buffers(B, 0), d_mean, d_value, False)     # the loss kernel's head gradients as the seed
         res[fused] = (pol.grad.clone(), stats.clone())
     (g1, s1), (g0, s0) = res[True], res[False]
     assert torch.allclose(s1[:9], s0[:9], rtol=2e-5, atol=1e-6 * max(1.0, s0[:9].abs().max().item())), (s1, s0)
     scale = g0.abs().max().item()
     assert (g1 - g0).abs().max().item() <= 5e-6 * scale, ((g1 - g0).abs().max().item(), scale)
     assert torch.allclose(g1[pol.log_std_off:], g0[pol.log_std_off:], rtol=1e-4, atol=1e-7)
+    # block by block, each on its own largest entry: fused against separate, and both against the fp64 network (3.0: the fill above)
+    assert_blocks_agree(pol, g1, g0, 5e-6, f"generated ppo update {name} B={B}")
+    assert_blocks(pol, g1, pin, f"generated ppo update {name} B={B} fused", untouched=3.0)
+    assert_blocks(pol, g0, pin, f"generated ppo update {name} B={B} separate", untouched=3.0)
 
 
 @pytest.mark.gpu
@@ -320,6 +333,7 @@ def test_generated_sac_actor_vs_torch_and_block_tile_kernel(name, ig, M):
     assert lib.vf_chain_plugin_launches() == n0 + 1 and mu.shape == ls.shape == (M, 4)
     sc = max(m0.abs().max().item(), v0.abs().max().item())
     assert (mu - m0.float()).abs().max().item() <= 2e-6 * sc and (ls - v0.float()).abs().max().item() <= 2e-6 * sc
+    pin = pinned_reference(pol, obs, pol._buffers(M, 0), d_mu, d_ls, ig)
     res = {}
     for fused in (True, False, True):
         pol.fused_backward = fused
@@ -336,6 +350,10 @@ def test_generated_sac_actor_vs_torch_and_block_tile_kernel(name, ig, M):
     for fused in (True, False):
         err = (res[fused][0] - gref).abs().max().item()
         assert err <= (1e-3 if M >= 16384 else 2e-6) * scale, (fused, err, scale)      # (a ReLU unit within rounding of 0 may flip vs fp64)
+        # the fp64 network given the kernel's side of those units: no escape at large M, every block and row on its own scale
+        assert_blocks(pol, res[fused][0], pin, f"generated sac actor {name} ig={ig} M={M} fused_backward={fused}")
+        for k, v in res[fused][1].items():
+            assert_rows(v, pin.d_in[k], pin.d_in32[k], f"generated sac actor {name} M={M} fused_backward={fused} {k}")
     for k in res[True][1]:
         assert torch.allclose(res[True][1][k], res[False][1][k], rtol=1e-4, atol=1e-6 * res[False][1][k].abs().max().item())
         want = xs[k].grad.float()
@@ -378,6 +396,7 @@ def test_generated_twin_critic_vs_torch_and_block_tile_kernel(name, M):
     b = pol._buffers(M, 0)
     bd = pol._bwd_desc(b, M, d_q0, d_q1, False)[0]
     assert lib.vf_mlp_backward_data_supported(C.byref(bd)) == 1                        # the generated class IS what runs
+    pin = pinned_reference(pol, obs, b, d_q0, d_q1, False)
     res = {}
     for fused in (True, False, True):
         pol.fused_backward = fused
@@ -394,6 +413,7 @@ def test_generated_twin_critic_vs_torch_and_block_tile_kernel(name, M):
     for fused in (True, False):                      # vs fp64: ReLU-mask flips at large M (test_sac_actor_chain_vs_torch_and_block_tile_kernel)
         err = (res[fused] - gref).abs().max().item()
         assert err <= (1e-3 if M >= 16384 else 2e-6) * scale, (fused, err, scale)
+        assert_blocks(pol, res[fused], pin, f"generated twin critic {name} M={M} fused_backward={fused}")      # (no large-M escape)
 
 
 @pytest.mark.gpu
@@ -428,11 +448,15 @@ def test_generated_fused_critic_step_equals_the_three_launch_step(name, M):
                 scr = torch.empty(int(L.vf_twin_q_loss_scratch_doubles(M)), dtype=torch.float64, device=DEV)
                 _lib.check(L.vf_twin_q_loss(_ptr(q0.view(-1)), _ptr(q1.view(-1)), _ptr(target), _ptr(dq0), _ptr(dq1), _ptr(loss), scr.data_ptr(), M, M, st))
                 c.backward(dq0.view(M, 1), dq1.view(M, 1), None)
+                pin = pinned_reference(c, obs, c._buffers(M, 0), dq0.view(M, 1), dq1.view(M, 1), False)
             out[fused] = (float(loss), c.grad[:c.n_params].clone())
     (l0, g0), (l1, g1) = out[False], out[True]
     assert abs(l0 - l1) <= 1e-6 * max(1.0, abs(l0)), (l0, l1)
     scale = g0.abs().max().item()
     assert scale > 0 and (g1 - g0).abs().max().item() <= 2e-6 * scale, ((g1 - g0).abs().max().item(), scale)
+    assert_blocks_agree(c, g1, g0, 2e-6, f"generated critic step {name} M={M}")
+    assert_blocks(c, g1, pin, f"generated critic step {name} M={M} fused")
+    assert_blocks(c, g0, pin, f"generated critic step {name} M={M} separate")
 
 
 @pytest.mark.gpu

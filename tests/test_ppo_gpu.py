@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import oracle
+from _gradcheck import assert_blocks, assert_blocks_agree, assert_rows, pinned_reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -239,11 +240,22 @@ def test_fused_ppo_step_of_a_tanh_or_elu_class_equals_separate_launches(acts, B)
                                        C.byref(cfg), scratch.data_ptr(), st()))
             pol.backward(d_mean, d_value, None)
             lib.vf_chain_plugin_set_enabled(1)
+            pin = pinned_reference(pol, obs, pol._buffers(B, 0), d_mean, d_value, False)
         res[fused] = (pol.grad.clone(), stats.clone())
     (g1, s1), (g0, s0) = res[True], res[False]
     assert torch.allclose(s1[:9], s0[:9], rtol=2e-5, atol=1e-6 * max(1.0, s0[:9].abs().max().item())), (s1, s0)
     scale = g0.abs().max().item()
     assert (g1 - g0).abs().max().item() <= (1e-4 if "tanh" in acts else 5e-6) * scale, ((g1 - g0).abs().max().item(), scale)
+    _fused_step_blocks(pol, g1, g0, pin, 1e-4 if "tanh" in acts else 5e-6, f"ppo update {acts} B={B}")
+
+
+def _fused_step_blocks(pol, g1, g0, pin, tol, what):
+    """a fused step's flat gradient g1 against that of its separate launches g0, block by block on each block's own largest entry, and
+    both against the fp64 network seeded with the separate branch's head gradients (tests/_gradcheck.py); the tests fill the gradient
+    with 3.0 before either branch"""
+    assert_blocks_agree(pol, g1, g0, tol, what)
+    assert_blocks(pol, g1, pin, what + " fused", untouched=3.0)
+    assert_blocks(pol, g0, pin, what + " separate", untouched=3.0)
 
 
 def test_ppo_without_policy_kwargs_builds_the_references_default_network_and_trains(monkeypatch):
@@ -586,6 +598,8 @@ def test_chain_backward_vs_torch_and_block_tile_kernel(M, net, mode):
             if prm.grad is None:
                 prm.grad = torch.zeros_like(prm)
     gref = ref.flat_grad().to(DEV)
+    pol.forward(obs)
+    pin = pinned_reference(pol, obs, pol._buffers(M, 0), d_mean, d_value, ig, second_head=d_value is not None)
     res = {}
     for fused in (True, False, True):
         pol.fused_backward = fused
@@ -602,6 +616,11 @@ def test_chain_backward_vs_torch_and_block_tile_kernel(M, net, mode):
         assert (gk - gref).abs().max().item() <= 5e-6 * scale, (fused, (gk - gref).abs().max().item(), scale)
         for k, v in res[fused][1].items():
             assert torch.allclose(v, xs[k].grad, rtol=1e-4, atol=1e-6 * xs[k].grad.abs().max().item())
+        # ... and every block / every row on its own scale, against the fp64 network (tests/_gradcheck.py); without a value-head
+        # gradient the value trunk's blocks keep the zeros put there
+        assert_blocks(pol, res[fused][0], pin, f"chain {net} {mode} M={M} fused_backward={fused}")
+        for k, v in res[fused][1].items():
+            assert_rows(v, pin.d_in[k], pin.d_in32[k], f"chain {net} {mode} M={M} fused_backward={fused} {k}")
     # accumulate mode
     pol.fused_backward = True
     pol.forward(obs)
@@ -640,6 +659,7 @@ def test_sac_actor_chain_vs_torch_and_block_tile_kernel(M, net, ig):
     b = pol._buffers(M, 0)
     bd = pol._bwd_desc(b, M, d_mu, d_ls, ig)[0]
     assert _lib.lib().vf_mlp_backward_data_supported(C.byref(bd)) == 1
+    pin = pinned_reference(pol, obs, b, d_mu, d_ls, ig)
     res = {}
     for fused in (True, False, True):
         pol.fused_backward = fused
@@ -662,6 +682,11 @@ def test_sac_actor_chain_vs_torch_and_block_tile_kernel(M, net, ig):
             want = xs[k].grad.float()
             bad = ((v - want).abs() > 1e-4 * want.abs() + 1e-5 * want.abs().max()).any(dim=1)
             assert int(bad.sum()) <= (8 if M >= 16384 else 0), (k, int(bad.sum()))
+        # against the fp64 network given the kernel's side of the units that flip: no escape at large M, every block and every row
+        # on its own scale (tests/_gradcheck.py)
+        assert_blocks(pol, res[fused][0], pin, f"sac actor {net} ig={ig} M={M} fused_backward={fused}")
+        for k, v in res[fused][1].items():
+            assert_rows(v, pin.d_in[k], pin.d_in32[k], f"sac actor {net} M={M} fused_backward={fused} {k}")
     for k in res[True][1]:                      # ... and the two implementations agree on every row
         assert torch.allclose(res[True][1][k], res[False][1][k], rtol=1e-4, atol=1e-6 * res[False][1][k].abs().max().item())
     pol.fused_backward = True
@@ -702,6 +727,7 @@ def test_twin_critic_chain_vs_torch_and_block_tile_kernel(M, net):
     b = pol._buffers(M, 0)
     bd = pol._bwd_desc(b, M, d_q0, d_q1, False)[0]
     assert _lib.lib().vf_mlp_backward_data_supported(C.byref(bd)) == 1                # the chain class IS what runs
+    pin = pinned_reference(pol, obs, b, d_q0, d_q1, False)
     res = {}
     for fused in (True, False, True):
         pol.fused_backward = fused
@@ -716,6 +742,93 @@ def test_twin_critic_chain_vs_torch_and_block_tile_kernel(M, net):
     for fused in (True, False):                      # vs fp64: ReLU-mask flips at large M (test_sac_actor_chain_vs_torch_and_block_tile_kernel)
         err = (res[fused] - gref).abs().max().item()
         assert err <= (1e-3 if M >= 16384 else 2e-6) * scale, (fused, err, scale)
+        assert_blocks(pol, res[fused], pin, f"twin critic {net} M={M} fused_backward={fused}")      # (no large-M escape: tests/_gradcheck.py)
+
+
+SWITCH_ROWS = [16384, 16385, 32768, 32769, 131071, 131072, 131073]      # chain16_ok's limit, chain_split_form's, wgrad_small's: each and one past
+
+
+@pytest.mark.parametrize("M", SWITCH_ROWS)
+@pytest.mark.parametrize("kind", ["sac_actor", "twin_critic", "ppo_nav"])
+def test_chain_backward_at_the_row_counts_where_the_launch_changes(kind, M):
+    """forward + reverse chain + row-slab weight gradients of the built-in classes at the row counts where the library changes the
+    launch: 16 384 (the 16-row forward form's last), 32 768 (the two-wave split's last) and 131 072, from which vf_mlp_wgrad.hip's
+    k_mlp_wgrad<true> runs -- two waves per SIMD, the other prefetch depth and slab plan; SHAC's critic over its 524 288-row horizon
+    buffer takes it on every iteration -- with 131 073 giving it an odd, ragged last slab.  Every block and every row on its own
+    scale against the fp64 network (tests/_gradcheck.py); two runs bit-identical."""
+    import ctypes as C
+    from visfly_amd import _lib
+    from visfly_amd.ppo import MlpPolicy
+    ext = {"state": [128, 64]}
+    if kind == "sac_actor":          # the BPTT / SHAC actor update: both heads, observation gradient
+        dims, ig, shapes = {"state": 13}, True, ((M, 4), (M, 4))
+        pol = MlpPolicy(dims, ext, [64, 64], [64, 64], DEV, seed=9, ortho_init=False, head_dims=(4, 4), log_std_param=False)
+    elif kind == "twin_critic":
+        dims, ig, shapes = {"state": 13, "action": 4}, False, ((M, 1), (M, 1))
+        pol = MlpPolicy(dims, ext, [64, 64], [64, 64], DEV, seed=11, ortho_init=False, head_dims=(1, 1), passthrough=("action",),
+                        log_std_param=False)
+    else:
+        dims, ig, shapes = {"state": 13, "target": 3}, False, ((M, 4), (M,))
+        pol = MlpPolicy(dims, {k: [128, 64] for k in dims}, [64, 64], [64, 64], DEV, seed=9)
+    g = torch.Generator(device=DEV).manual_seed(M)
+    obs = {k: torch.randn((M, d), device=DEV, generator=g) for k, d in dims.items()}
+    if "action" in obs:
+        obs["action"] = torch.tanh(obs["action"])
+    d0, d1 = (torch.randn(s, device=DEV, generator=g) / M for s in shapes)
+    h0, h1 = pol.forward(obs)
+    b = pol._buffers(M, 0)
+    bd = pol._bwd_desc(b, M, d0, d1, ig)[0]
+    assert _lib.lib().vf_mlp_backward_data_supported(C.byref(bd)) == 1               # the chain class IS what runs
+    pin = pinned_reference(pol, obs, b, d0, d1, ig)
+    sc = max(pin.mean.abs().max().item(), pin.value.abs().max().item())
+    assert (h0.double() - pin.mean).abs().max().item() <= 2e-6 * sc and (h1.double().view(M, -1) - pin.value).abs().max().item() <= 2e-6 * sc
+    runs = []
+    for _ in range(2):
+        pol.grad.fill_(0.0)
+        pol.forward(obs)
+        d_in = pol.backward(d0, d1, None, need_input_grad=ig)
+        runs.append((pol.grad.clone(), {k: v.clone() for k, v in d_in.items()}))
+    assert torch.equal(runs[0][0], runs[1][0]) and all(torch.equal(v, runs[1][1][k]) for k, v in runs[0][1].items())
+    assert_blocks(pol, runs[0][0], pin, f"switch {kind} M={M}")
+    assert (set(runs[0][1]) == {"state"}) == ig
+    for k, v in runs[0][1].items():
+        assert_rows(v, pin.d_in[k], pin.d_in32[k], f"switch {kind} M={M} {k}")
+
+
+@pytest.mark.parametrize("M", [32768, 32769])
+def test_fused_critic_step_either_side_of_the_row_count_where_the_form_changes(M, monkeypatch):
+    """vf_twin_q_update of the built-in twin-critic class with the form left to the library (two half-network waves per row tile up to
+    32 768 rows, one wave per tile past it) against forward / vf_twin_q_loss / backward: the loss, and the flat gradient block by block
+    (test_shac_gpu.py::test_fused_critic_step_equals_the_three_launch_step forces either form at 1000 and 4113 rows)"""
+    from visfly_amd.ppo import MlpPolicy, _ptr
+    monkeypatch.delenv("VISFLY_AMD_CHAIN_SPLIT", raising=False)
+    _lib, lib = L()
+    c = MlpPolicy({"state": 13, "action": 4}, {"state": [128, 64]}, [64, 64], [64, 64], DEV, seed=3, ortho_init=False, head_dims=(1, 1),
+                  passthrough=("action",), log_std_param=False)
+    g = torch.Generator(device=DEV).manual_seed(M)
+    obs = {"state": torch.randn((M, 13), device=DEV, generator=g), "action": torch.tanh(torch.randn((M, 4), device=DEV, generator=g))}
+    target = torch.randn(M, device=DEV, generator=g)
+    out = {}
+    for fused in (False, True):
+        c.grad.fill_(0.0)
+        loss = torch.empty(1, device=DEV)
+        if fused:
+            assert c.twin_q_update(obs, target, loss, M), "the reference's critic shape must run on vf_twin_q_update"
+        else:
+            q0, q1 = c.forward(obs, save_activations=True)
+            dq0, dq1 = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+            scr = torch.empty(int(lib.vf_twin_q_loss_scratch_doubles(M)), dtype=torch.float64, device=DEV)
+            _lib.check(lib.vf_twin_q_loss(_ptr(q0.view(-1)), _ptr(q1.view(-1)), _ptr(target), _ptr(dq0), _ptr(dq1), _ptr(loss), scr.data_ptr(), M, M, st()))
+            c.backward(dq0.view(M, 1), dq1.view(M, 1), None)
+            pin = pinned_reference(c, obs, c._buffers(M, 0), dq0.view(M, 1), dq1.view(M, 1), False)
+        out[fused] = (float(loss), c.grad[:c.n_params].clone())
+    (l0, g0), (l1, g1) = out[False], out[True]
+    assert abs(l0 - l1) <= 1e-6 * max(1.0, abs(l0)), (l0, l1)
+    scale = g0.abs().max().item()
+    assert scale > 0 and (g1 - g0).abs().max().item() <= 2e-6 * scale, ((g1 - g0).abs().max().item(), scale)
+    assert_blocks_agree(c, g1, g0, 2e-6, f"critic step M={M}")
+    assert_blocks(c, g1, pin, f"critic step M={M} fused")
+    assert_blocks(c, g0, pin, f"critic step M={M} separate")
 
 
 @pytest.mark.parametrize("shape", ["reference", "other"])
@@ -754,6 +867,7 @@ def test_policy_only_forward_and_split_backward(shape):
     pol.weight_grad_slots(M, n, d_means, accumulate=True)
     scale = want.abs().max().item()
     assert (pol.grad - want).abs().max().item() <= 2e-6 * scale
+    assert_blocks_agree(pol, pol.grad, want, 2e-6, "weight_grad_slots vs per-slot backward")       # ... and block by block
 
 
 @pytest.mark.parametrize("form", ["split", "one-wave"])
@@ -764,6 +878,19 @@ def test_fused_ppo_update_equals_separate_launches(net, B, form, monkeypatch):
     vs forward / vf_ppo_loss / backward: same statistics, same gradient (up to fp32 summation order) -- in both forms of the fused
     kernel: two half-network waves per row tile (k_ppo_update_split, the default) and one wave per tile (k_ppo_update_chain)"""
     monkeypatch.setenv("VISFLY_AMD_CHAIN_SPLIT", "1" if form == "split" else "0")     # read by the library per call
+    _fused_ppo_update_vs_separate_launches(net, B, form)
+
+
+@pytest.mark.parametrize("net", ["nav", "hover"])
+@pytest.mark.parametrize("B", [32768, 32769])
+def test_fused_ppo_update_either_side_of_the_row_count_where_the_form_changes(net, B, monkeypatch):
+    """the same with the form left to the library (chain_split_form: two half-network waves per row tile up to 32 768 rows, one wave
+    per tile past it), at the last row count of the one and the first of the other"""
+    monkeypatch.delenv("VISFLY_AMD_CHAIN_SPLIT", raising=False)
+    _fused_ppo_update_vs_separate_launches(net, B, "form of the library's choice")
+
+
+def _fused_ppo_update_vs_separate_launches(net, B, form):
     from visfly_amd.ppo import MlpPolicy
     _lib, lib = L()
     dims = {"state": 13, "target": 3} if net == "nav" else {"state": 13}
@@ -793,12 +920,14 @@ def test_fused_ppo_update_equals_separate_launches(net, B, form, monkeypatch):
                                        adv.data_ptr(), ret.data_ptr(), d_mean.data_ptr(), d_value.data_ptr(), stats.data_ptr(), B,
                                        C.byref(cfg), scratch.data_ptr(), st()))
             pol.backward(d_mean, d_value, None)
+            pin = pinned_reference(pol, obs, pol._buffers(B, 0), d_mean, d_value, False)     # the loss kernel's head gradients as the seed
         res[fused] = (pol.grad.clone(), stats.clone())
     (g1, s1), (g0, s0) = res[True], res[False]
     assert torch.allclose(s1[:9], s0[:9], rtol=2e-5, atol=1e-6 * max(1.0, s0[:9].abs().max().item())), (s1, s0)
     scale = g0.abs().max().item()
     assert (g1 - g0).abs().max().item() <= 5e-6 * scale, ((g1 - g0).abs().max().item(), scale)
     assert torch.allclose(g1[pol.log_std_off:], g0[pol.log_std_off:], rtol=1e-4, atol=1e-7)
+    _fused_step_blocks(pol, g1, g0, pin, 5e-6, f"ppo update {net} B={B} {form}")
 
 
 @pytest.mark.parametrize("form", ["split", "one-wave"])
@@ -841,6 +970,11 @@ def test_fused_ppo_update_on_an_indexed_minibatch(net, vclip, B, form, monkeypat
                 assert torch.equal(copies[k], o[k]), "the observation rows the indexed launch left for the weight gradients"
         res[indexed] = (pol.grad.clone(), stats.clone())
     assert torch.equal(res[True][1], res[False][1]) and torch.equal(res[True][0], res[False][0])
+    # ... and that gradient, block by block on each block's own scale, is the fp64 network's for the head gradients the launch left
+    # where the weight gradients read them (tests/_gradcheck.py)
+    b = pol._buffers(B, 0)
+    pin = pinned_reference(pol, o, b, b["d:mean"], b["d:value"], False)
+    assert_blocks(pol, res[False][0], pin, f"indexed ppo update {net} B={B} {form}", untouched=3.0)
 
 
 def test_ppo_training_with_indexed_minibatches_equals_the_shuffled_copy():

@@ -237,10 +237,20 @@ def test_fused_critic_step_equals_the_three_launch_step(M, form, monkeypatch):
         algo._dq = None
         loss = algo._critic_step_once(obs, act, target)
         out[fused] = (float(loss), c.grad[:c.n_params].cpu().numpy().copy())
+        if not fused:        # the loss kernel's head gradients and the saved activations of the three-launch step: the seed of the reference
+            dq, saved = [t.clone().view(M, 1) for t in algo._dq[:2]], {k: v.clone() for k, v in c._buffers(M, 0).items() if torch.is_tensor(v)}
     assert c._fused_twin_q is not False, "the reference's critic shape must run on vf_twin_q_update"
     (l0, g0), (l1, g1) = out[False], out[True]
     assert abs(l0 - l1) <= 1e-6 * max(1.0, abs(l0)), (l0, l1)
     rel = blocks_close(g1, g0, c, 2e-6, 1e-4, "fused critic gradient")
+    # every block on its own largest entry (no floor): fused against the three launches, and both against the fp64 network on the
+    # parameters the steps started from (tests/_gradcheck.py)
+    from _gradcheck import assert_blocks, assert_blocks_agree, pinned_reference
+    c.flat[:c.n_params].copy_(torch.from_numpy(fx["critic_params0"]))
+    pin = pinned_reference(c, {"state": obs["state"], "action": act}, saved, dq[0], dq[1], False)
+    assert_blocks_agree(c, torch.from_numpy(g1), torch.from_numpy(g0), 2e-6, f"critic step M={M} {form}")
+    assert_blocks(c, torch.from_numpy(g1), pin, f"critic step M={M} {form} fused")
+    assert_blocks(c, torch.from_numpy(g0), pin, f"critic step M={M} {form} separate")
     print(f"M={M}: loss {l1:.7f} vs {l0:.7f}, gradient rel err {rel:.2e}")
     env.close()
 

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from _gradcheck import check_policy_vs_autograd as _check_policy_vs_autograd
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -150,76 +152,6 @@ def test_dispatch_boundary_and_limits():
         for fn in (lib.vf_linear_bwd_weight, lib.vf_linear_bwd_weight_acc):
             assert fn(t.data_ptr(), No, None, 0, t.data_ptr(), K, t.data_ptr(), t.data_ptr(), 1, K, No, t.data_ptr(), 0, st()) == EINVAL
     assert lib.vf_linear_fwd(t.data_ptr(), 256, t.data_ptr(), t.data_ptr(), t.data_ptr(), 256, 1, 256, 256, 5, st()) == EINVAL
-
-
-def _check_policy_vs_autograd(pol, obs, d0, d1, need_input_grad=True):
-    """forward and backward(need_input_grad) of a layer-by-layer network against autograd of to_torch() in fp64; every parameter block
-    and every observation gradient is held to 2e-5 of its scale OR three times the distance of torch's own fp32 autograd from the fp64
-    reference, whichever is larger (mode (c) of test_policy_with_other_activations_vs_torch).
-    ReLU: a unit whose pre-activation lies within fp32 rounding of zero can be on in fp32 and off in fp64 (or the reverse); that one
-    unit then moves whole gradient entries by ~1 / M, far above the rounding the bound is about (test_ppo_gpu.py::
-    test_sac_actor_chain_vs_torch_and_block_tile_kernel meets the same at M >= 16384).  So the fp64 reference is given the side the
-    kernel's saved output shows for exactly those units -- and every such unit must have |z| below the forward tolerance of the layer
-    entry points (1e-5 sqrt(K), relative to 1 + the row's largest |z|), else it is an error of the forward and the test fails."""
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        mean, value = pol.forward(obs)
-    mean, value = mean.clone(), value.clone()
-    M = mean.shape[0]
-    saved = pol._buffers(M, 0)
-    ref = pol.to_torch().double().to(DEV)
-    flips = []
-
-    def side_of_kernel(ly):
-        def hook(mod, inp, z):
-            on = saved[ly.dst][:, ly.dc:ly.dc + ly.No] > 0
-            flip = on != (z > 0)
-            if bool(flip.any()):
-                lim = 1e-5 * np.sqrt(ly.K) * (1 + z.detach().abs().max(dim=1, keepdim=True).values)
-                assert bool((z.detach().abs() <= lim)[flip].all()), (ly.dst, float(z.detach().abs()[flip].max()))
-                flips.append(int(flip.sum()))
-            side = torch.where(on, torch.full_like(z, 1e-300), torch.zeros_like(z))      # relu' = 1 | 0 there, the value stays ~0
-            return torch.where(flip, side + (z - z.detach()), z)
-        return hook
-    for ly, m in zip(pol.layers, ref.lin):
-        if ly.relu == 1:
-            m.register_forward_hook(side_of_kernel(ly))
-    xs = {k: v.double().requires_grad_(True) for k, v in obs.items()}
-    m0, v0 = ref(xs)
-    ((m0 * d0.double()).sum() + (v0.view(d1.shape) * d1.double()).sum()).backward()
-    print(f"ReLU units the fp64 reference was given the kernel's side of: {sum(flips)}")
-    gref = ref.flat_grad().to(DEV)[:pol.n_params]
-    ref32 = pol.to_torch().to(DEV)
-    x32 = {k: v.clone().requires_grad_(True) for k, v in obs.items()}
-    m32, v32 = ref32(x32)
-    ((m32 * d0).sum() + (v32.view(d1.shape) * d1).sum()).backward()
-    g32 = ref32.flat_grad().to(DEV).double()[:pol.n_params]
-    sc = max(m0.abs().max().item(), v0.abs().max().item(), 1e-3)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        e = max((mean.double() - m0).abs().max().item(), (value.double() - v0.view(value.shape)).abs().max().item())
-        print(f"forward: max abs err {e:.3e} of scale {sc:.3e}")
-        assert e <= 4e-6 * sc
-        d_in = pol.backward(d0, d1, None, need_input_grad=need_input_grad)
-    for ly in pol.layers:
-        if ly.frozen:
-            continue
-        for lo, hi in ((ly.w_off, ly.w_off + ly.K * ly.No), (ly.b_off, ly.b_off + ly.No)):
-            bs = max(gref[lo:hi].abs().max().item(), 1e-3 * gref.abs().max().item())
-            bound = max(2e-5 * bs, 3.0 * (g32[lo:hi] - gref[lo:hi]).abs().max().item())
-            err = (pol.grad[lo:hi].double() - gref[lo:hi]).abs().max().item()
-            assert err <= bound, (ly.src, ly.dst, err / bs, bound / bs)
-    for k, v in d_in.items():
-        if xs[k].grad is None:
-            continue
-        bound = max(2e-5 * max(xs[k].grad.abs().max().item(), 1e-12), 3.0 * (x32[k].grad.double() - xs[k].grad).abs().max().item())
-        assert (v.double() - xs[k].grad).abs().max().item() <= bound, k
-    g1 = pol.grad.clone()
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        pol.forward(obs)
-        pol.backward(d0, d1, None, need_input_grad=need_input_grad)
-    assert torch.equal(g1, pol.grad), "two runs differ"
 
 
 @pytest.mark.parametrize("act", ["relu", "tanh"])
