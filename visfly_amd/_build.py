@@ -23,7 +23,9 @@ _PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 # threshold decides about the rest (drag, integrators, controller, epilogue).  Re-scanned over 0 .. 24 with the hand-packed loop on a probe
 # kernel around control_interval_pairs: 265-268 instructions for 0 .. 8, 271-273 above; in k_env_step itself 264 at 8 (120 packed, 2 moves),
 # 265 at 4 (profiles/env_pair_algebra.txt; before the hand packing: 315 at the default, 301 at 8, profiles/r04_env_timeline.txt): 8 stays.
-# Same IEEE operations: bit-identical.
+# Same IEEE operations: bit-identical.  The threshold never reaches the divisions: an fp32 `/` is expanded in the backend, after the
+# vectoriser has run, so the plain operations of two quotients are paired by hand as well (div_p2 / div_p1 in vf_pair_algebra.hpp:
+# k_env_step's loop 263 -> 247, profiles/env_pair_division.txt).
 _STEP = _PRELOAD + ["-mllvm", "-slp-threshold=8"]
 PER_SOURCE_FLAGS = {"vf_env.hip": _STEP, "vf_dyn.hip": _STEP}
 

@@ -323,8 +323,17 @@ __device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const Quat& q, c
     acc[2] = ra.z / c.m + c.g_z;
 }
 
-// ... on pairs
-__device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const QuatP& q, const float* v, float F, const float* kl,
+// The constants the pair forms' sub-step loop reads, loaded once in front of it: the pair divisions carry scheduling barriers
+// (vf_pair_algebra.hpp), and hipcc hoists no load out of a loop that holds one.
+struct SubstepCfg {
+    float dt, m, g_z;
+    int interval_steps;
+};
+__device__ __forceinline__ SubstepCfg substep_cfg(const vf_dyn_cfg& c) { return SubstepCfg{c.dt, c.m, c.g_z, c.interval_steps}; }
+
+// ... on pairs (C: vf_dyn_cfg or SubstepCfg)
+template <class C>
+__device__ __forceinline__ void linear_acc(const C& c, const QuatP& q, const float* v, float F, const float* kl,
                                            const float* kq, float* acc)
 {
     const QuatP vq{pair_of(0.0f, v[0] + 0.0f), pair_of(v[1] + 0.0f, v[2] + 0.0f)};
@@ -338,14 +347,17 @@ __device__ __forceinline__ void linear_acc(const vf_dyn_cfg& c, const QuatP& q, 
     const vf_f2 u12 = zf12 - (kl12 * vb.yz + (kq12 * vb.yz) * ab12);
     const QuatP uq{pair_of(0.0f, ux), u12};
     const QuatP ra = qmul_p<false, true>(qmul_p<false, false>(q, uq), q);     // q * (0, u) * conj(q)
-    acc[0] = ra.wx[1] / c.m + 0.0f;
-    acc[1] = ra.yz[0] / c.m + 0.0f;
-    acc[2] = ra.yz[1] / c.m + c.g_z;
+    vf_f2 a12;                                 // the IEEE divisions, the plain operations of (y, z) on the pair (vf_pair_algebra.hpp)
+    float a0;
+    div_p1(ra.yz, ra.wx[1], c.m, a12, a0);
+    acc[0] = a0 + 0.0f;
+    acc[1] = a12[0] + 0.0f;
+    acc[2] = a12[1] + c.g_z;
 }
 
 // translation: acc, then p and v advance (maths.py:310,344,346 / repaired rk4 :353-386).  Q: Quat (scalar form) or QuatP (pairs)
-template <int INTEG, class Q>
-__device__ __forceinline__ void trans_substep(const vf_dyn_cfg& c, const Q& q, float F, const float* kl, const float* kq,
+template <int INTEG, class Q, class C>
+__device__ __forceinline__ void trans_substep(const C& c, const Q& q, float F, const float* kl, const float* kq,
                                               const float* wind, float* p, float* v, float* acc)
 {
     linear_acc(c, q, v, F, kl, kq, acc);
@@ -381,8 +393,8 @@ __device__ __forceinline__ void trans_substep(const vf_dyn_cfg& c, const Q& q, f
 // (maths.py:311,314,345,347,351; dynamics.py:367; repaired rk4: SURVEY App. C-1 -- stages see the
 // caller's wind, ks-contractions are ((k1*w0 + k2*w1) + k3*w2) + k4*w3, tau stays frozen).
 // On pairs: q = (w, x), (y, z); wq = (0, w) as a pure-vector quaternion (its zero is carried, never written)
-template <int INTEG>
-__device__ __forceinline__ void rot_substep(const vf_dyn_cfg& c, const IntervalMats& M, const vf_f2 ft01, const vf_f2 ft23, QuatP& q,
+template <int INTEG, class C>
+__device__ __forceinline__ void rot_substep(const C& c, const IntervalMats& M, const vf_f2 ft01, const vf_f2 ft23, QuatP& q,
                                             QuatP& wq, float* aa)
 {
     const float dt = c.dt;
@@ -428,8 +440,7 @@ __device__ __forceinline__ void rot_substep(const vf_dyn_cfg& c, const IntervalM
     }
     const vf_f2 s01 = q.wx * q.wx, s23 = q.yz * q.yz;
     const float nn = sqrtf(((s01[0] + s01[1]) + s23[0]) + s23[1]);   // :367, maths.py:226-230
-    q.wx = pair_of(q.wx[0] / nn, q.wx[1] / nn);
-    q.yz = pair_of(q.yz[0] / nn, q.yz[1] / nn);
+    div_p2(q.wx, q.yz, nn, q.wx, q.yz);
 }
 // ... on scalars, tq = tau
 template <int INTEG>
@@ -576,16 +587,17 @@ __device__ __forceinline__ void control_interval_pairs(const vf_dyn_cfg& c, Agen
         s.q = to_quat(q);
         s.w[0] = wq.wx[1]; s.w[1] = wq.yz[0]; s.w[2] = wq.yz[1];
     };
+    const SubstepCfg sc = substep_cfg(c);
 #pragma unroll 1
-    for (int sub = 0; sub < c.interval_steps; ++sub) {
+    for (int sub = 0; sub < sc.interval_steps; ++sub) {
         if constexpr (!__is_same(CK, NoCheckpoint)) {   // an observer reads the agent at the head of the sub-step
             if (sub != 0) mirror();
             ck.head(sub, s);
         }
         vf_f2 ft01, ft23;
         motor_substep<CTRL_DELAY>(M.k, M.B, r.Td, r.wd, r.wm, r.T, ft01, ft23);
-        trans_substep<INTEG>(c, q, ft01[0], kl, kq, s.wnd, s.p, s.v, s.acc);   // uses q of the sub-step start
-        rot_substep<INTEG>(c, M, ft01, ft23, q, wq, s.aa);
+        trans_substep<INTEG>(sc, q, ft01[0], kl, kq, s.wnd, s.p, s.v, s.acc);   // uses q of the sub-step start
+        rot_substep<INTEG>(sc, M, ft01, ft23, q, wq, s.aa);
     }
     mirror();
     ck.end(s);
@@ -843,13 +855,14 @@ __device__ __forceinline__ void split_rotation_wave(const vf_dyn_cfg& c, const D
     const IntervalMats M = interval_mats(c);
     RotorsP r(s, Td, wd);
     QuatP q = to_pairs(s.q), wq{pair_of(0.0f, s.w[0]), pair_of(s.w[1], s.w[2])};
-    for (int sub = 0; sub < c.interval_steps; ++sub) {
+    const SubstepCfg sc = substep_cfg(c);
+    for (int sub = 0; sub < sc.interval_steps; ++sub) {
         vf_f2 ft01, ft23;
         motor_substep<CTRL_DELAY>(M.k, M.B, r.Td, r.wd, r.wm, r.T, ft01, ft23);
         float(*x)[64] = sh.xq[sub & 1];
         x[0][l] = q.wx[0]; x[1][l] = q.wx[1]; x[2][l] = q.yz[0]; x[3][l] = q.yz[1]; x[4][l] = ft01[0];
         lds_publish_barrier();
-        rot_substep<INTEG>(c, M, ft01, ft23, q, wq, s.aa);
+        rot_substep<INTEG>(sc, M, ft01, ft23, q, wq, s.aa);
     }
     r.store(s);
     s.q = to_quat(q);
@@ -886,12 +899,13 @@ __device__ __forceinline__ void split_translation_wave(const vf_dyn_cfg& c, cons
     const int Dd = D >= 0 ? D : c.delay_steps;
     if (Dd > 0)    // same head update ring_exchange applies (the rotation wave did the exchange itself)
         sp.vel = __int_as_float(g.head + 1 == Dd ? 0 : g.head + 1);
-    for (int sub = 0; sub < c.interval_steps; ++sub) {
+    const SubstepCfg sc = substep_cfg(c);
+    for (int sub = 0; sub < sc.interval_steps; ++sub) {
         __builtin_amdgcn_s_barrier();
         const float(*x)[64] = sh.xq[sub & 1];
         const QuatP q{pair_of(x[0][l], x[1][l]), pair_of(x[2][l], x[3][l])};
         const float F = x[4][l];
-        trans_substep<INTEG>(c, q, F, kl, kq, s.wnd, s.p, s.v, s.acc);
+        trans_substep<INTEG>(sc, q, F, kl, kq, s.wnd, s.p, s.v, s.acc);
     }
     __builtin_amdgcn_s_barrier();
     const float(*f)[64] = sh.fin;

@@ -4,14 +4,16 @@
 // that slot (profiles/r02_valu_cost_probe.txt), so the sub-step loop pays per instruction, not per operation.  The pair layout keeps a
 // quaternion as two 64-bit register pairs (w, x) and (y, z); the Hamilton product on it is ONE asm statement of 8 packed multiplies and
 // 6 packed adds whose swaps and sign flips ride on op_sel / op_sel_hi / neg_lo / neg_hi.  The constant matrices are applied two rows at a
-// time from column pairs (A[r][k], A[r+1][k]) arranged once per control interval.
+// time from column pairs (A[r][k], A[r+1][k]) arranged once per control interval.  The IEEE divisions keep hipcc's own sequence with the
+// six plain operations of two quotients on a pair (div_p, div_p2, div_p1 at the end of this file).
 //
 // Same products, same additions, same order as the scalar forms (utils/maths.py:168-174; the k-ordered FMA chains of the reference's
 // sgemm).  The only rewrites are (-a) * b for -(a * b) and x + (-y) for x - y, both exact in IEEE arithmetic, signed zeros included;
 // a pure-vector operand (0, v) keeps its zero and every term.  Each pair operation has a plain C++ body of the same operation order for
 // the host (tests/test_pair_algebra_host.py compiles both forms with the system compiler and compares them bit for bit).
 //
-// Self-contained: no HIP header needed, so that the host test can include it.  Compile with -ffp-contract=off.
+// Self-contained: no HIP header needed (compiler builtins only on the device side), so that the host test can include it.  Compile with
+// -ffp-contract=off.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -282,6 +284,138 @@ VF_PA_FN void mat3_p(const Mat3P& A, const vf_f2 x0p, const vf_f2 x12, float& o0
                   __builtin_fmaf(A.c12[2][1], x12[1], __builtin_fmaf(A.c12[1][1], x12[0], A.c12[0][1] * x0p[1])));
 #endif
     o0 = __builtin_fmaf(A.r0[2], x12[1], __builtin_fmaf(A.r0[1], x12[0], A.r0[0] * x0p[1]));
+}
+
+// ---- IEEE division of a pair --------------------------------------------------------------------------------------------------------
+// hipcc expands an fp32 `/` in the backend, after the SLP vectoriser has run, into 11 instructions that can never be paired:
+//   d = v_div_scale(b, b, a)   n = v_div_scale(a, b, a) (writes the flag v_div_fmas reads)   r = v_rcp(d)
+//   e = fma(-d, r, 1)   r = fma(e, r, r)   q = n * r   e = fma(-d, q, n)   q = fma(e, r, q)   e = fma(-d, q, n)
+//   v_div_fixup(v_div_fmas(e, r, q), b, a)
+// div_p restates that sequence (order and negated operand read off the compiler's own code for `/`) with the six plain operations on the
+// pair: v_div_scale, v_rcp, v_div_fmas and v_div_fixup per half with the same operands, the six as v_pk_fma_f32 / v_pk_mul_f32 (the
+// negations on neg_lo / neg_hi).  17 instructions for two quotients instead of 22, and the same correctly rounded quotient for every
+// input -- specials, denormals and the scaled cases included; there is no guard and no range assumption
+// (tools/div_pair_probe.hip compares it with `/` bit for bit).  Written with the compiler's builtins, not as an asm statement: the
+// flag of each half stays a value the compiler moves into VCC itself (s_mov_b64 vcc, s[..], as in its own schedules), the scaled halves
+// land in one register pair without a move, and the wait states around v_rcp / VCC / v_div_fmas remain the compiler's.
+#if defined(__HIP_DEVICE_COMPILE__)
+VF_PA_FN vf_f2 div_p(const vf_f2 a, const vf_f2 b)
+{
+    bool f0, f1, unused;
+    const vf_f2 d = {__builtin_amdgcn_div_scalef(a[0], b[0], false, &unused), __builtin_amdgcn_div_scalef(a[1], b[1], false, &unused)};
+    const vf_f2 n = {__builtin_amdgcn_div_scalef(a[0], b[0], true, &f0), __builtin_amdgcn_div_scalef(a[1], b[1], true, &f1)};
+    vf_f2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    const vf_f2 one = {1.0f, 1.0f};
+    vf_f2 e = __builtin_elementwise_fma(-d, r, one);
+    r = __builtin_elementwise_fma(e, r, r);
+    vf_f2 q = n * r;
+    e = __builtin_elementwise_fma(-d, q, n);
+    q = __builtin_elementwise_fma(e, r, q);
+    e = __builtin_elementwise_fma(-d, q, n);
+    return pair_of(__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e[0], r[0], q[0], f0), b[0], a[0]),
+                   __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e[1], r[1], q[1], f1), b[1], a[1]));
+}
+#else
+VF_PA_FN vf_f2 div_p(const vf_f2 a, const vf_f2 b) { return pair_of(a[0] / b[0], a[1] / b[1]); }
+#endif
+// ... one denominator for both halves (the two scalings of it still differ: they depend on the numerator)
+VF_PA_FN vf_f2 div_p(const vf_f2 a, const float b) { return div_p(a, pair_of(b, b)); }
+
+// A lone div_p is a chain of six packed instructions each reading the one before, and hipcc pads every such pair with an s_nop, which a
+// lone wave pays like an instruction; left to itself its scheduler runs neighbouring divisions' chains one after the other.  The two
+// forms below are div_p and a second division with their steps ALTERNATING, the order pinned by a scheduling barrier after each step
+// (no VALU or transcendental instruction moves across VF_PA_SB, mask 0x3FC lets the other kinds pass; registers, the flags' way into
+// VCC and every wait state remain the compiler's): the second chain fills the pads of the first.  hipcc hoists no load out of a loop
+// that holds such a barrier, so what the loop reads from memory is loaded in front of it (SubstepCfg in vf_dyn_device.hpp).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VF_PA_SB __builtin_amdgcn_sched_barrier(0x3FC)
+#define VF_PA_SCALE2(a, b, num, fl0, fl1) {__builtin_amdgcn_div_scalef(a[0], b, num, &fl0), __builtin_amdgcn_div_scalef(a[1], b, num, &fl1)}
+#define VF_PA_FINISH(e, r, q, fl, b, a) __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e, r, q, fl), b, a)
+#endif
+// (o0, o1) = (a0 / b, a1 / b): the quaternion's normalisation
+VF_PA_FN void div_p2(const vf_f2 a0, const vf_f2 a1, const float b, vf_f2& o0, vf_f2& o1)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    bool f00, f01, f10, f11, unused;
+    const vf_f2 one = {1.0f, 1.0f};
+    const vf_f2 d0 = VF_PA_SCALE2(a0, b, false, unused, unused), d1 = VF_PA_SCALE2(a1, b, false, unused, unused);
+    vf_f2 r0 = {__builtin_amdgcn_rcpf(d0[0]), __builtin_amdgcn_rcpf(d0[1])}, r1 = {__builtin_amdgcn_rcpf(d1[0]), __builtin_amdgcn_rcpf(d1[1])};
+    const vf_f2 n0 = VF_PA_SCALE2(a0, b, true, f00, f01), n1 = VF_PA_SCALE2(a1, b, true, f10, f11);
+    VF_PA_SB;
+    vf_f2 e0 = __builtin_elementwise_fma(-d0, r0, one);
+    VF_PA_SB;
+    vf_f2 e1 = __builtin_elementwise_fma(-d1, r1, one);
+    VF_PA_SB;
+    r0 = __builtin_elementwise_fma(e0, r0, r0);
+    VF_PA_SB;
+    r1 = __builtin_elementwise_fma(e1, r1, r1);
+    VF_PA_SB;
+    vf_f2 q0 = n0 * r0;
+    VF_PA_SB;
+    vf_f2 q1 = n1 * r1;
+    VF_PA_SB;
+    e0 = __builtin_elementwise_fma(-d0, q0, n0);
+    VF_PA_SB;
+    e1 = __builtin_elementwise_fma(-d1, q1, n1);
+    VF_PA_SB;
+    q0 = __builtin_elementwise_fma(e0, r0, q0);
+    VF_PA_SB;
+    q1 = __builtin_elementwise_fma(e1, r1, q1);
+    VF_PA_SB;
+    e0 = __builtin_elementwise_fma(-d0, q0, n0);
+    VF_PA_SB;
+    e1 = __builtin_elementwise_fma(-d1, q1, n1);
+    VF_PA_SB;
+    o0 = pair_of(VF_PA_FINISH(e0[0], r0[0], q0[0], f00, b, a0[0]), VF_PA_FINISH(e0[1], r0[1], q0[1], f01, b, a0[1]));
+    o1 = pair_of(VF_PA_FINISH(e1[0], r1[0], q1[0], f10, b, a1[0]), VF_PA_FINISH(e1[1], r1[1], q1[1], f11, b, a1[1]));
+#else
+    o0 = div_p(a0, b);
+    o1 = div_p(a1, b);
+#endif
+}
+// (o, ox) = (a / b, ax / b), the second a single quotient by the same sequence on scalars: the three components of a vector
+VF_PA_FN void div_p1(const vf_f2 a, const float ax, const float b, vf_f2& o, float& ox)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    bool f0, f1, fx, unused;
+    const vf_f2 one = {1.0f, 1.0f};
+    const vf_f2 d = VF_PA_SCALE2(a, b, false, unused, unused);
+    const float dx = __builtin_amdgcn_div_scalef(ax, b, false, &unused);
+    vf_f2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    float rx = __builtin_amdgcn_rcpf(dx);
+    const vf_f2 n = VF_PA_SCALE2(a, b, true, f0, f1);
+    const float nx = __builtin_amdgcn_div_scalef(ax, b, true, &fx);
+    VF_PA_SB;
+    vf_f2 e = __builtin_elementwise_fma(-d, r, one);
+    VF_PA_SB;
+    float ex = __builtin_fmaf(-dx, rx, 1.0f);
+    VF_PA_SB;
+    r = __builtin_elementwise_fma(e, r, r);
+    VF_PA_SB;
+    rx = __builtin_fmaf(ex, rx, rx);
+    VF_PA_SB;
+    vf_f2 q = n * r;
+    VF_PA_SB;
+    float qx = nx * rx;
+    VF_PA_SB;
+    e = __builtin_elementwise_fma(-d, q, n);
+    VF_PA_SB;
+    ex = __builtin_fmaf(-dx, qx, nx);
+    VF_PA_SB;
+    q = __builtin_elementwise_fma(e, r, q);
+    VF_PA_SB;
+    qx = __builtin_fmaf(ex, rx, qx);
+    VF_PA_SB;
+    e = __builtin_elementwise_fma(-d, q, n);
+    VF_PA_SB;
+    ex = __builtin_fmaf(-dx, qx, nx);
+    VF_PA_SB;
+    o = pair_of(VF_PA_FINISH(e[0], r[0], q[0], f0, b, a[0]), VF_PA_FINISH(e[1], r[1], q[1], f1, b, a[1]));
+    ox = VF_PA_FINISH(ex, rx, qx, fx, b, ax);
+#else
+    o = div_p(a, b);
+    ox = ax / b;
+#endif
 }
 
 }  // namespace vf
