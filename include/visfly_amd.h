@@ -507,6 +507,24 @@ int vf_linear_bwd_weight_acc(const float* dY, int32_t lddy, const float* Ymask, 
                              int32_t ldx, float* dW, float* db, int32_t M, int32_t K, int32_t No, float* scratch,
                              int32_t act, vf_stream_t stream);
 
+/* nn.LayerNorm(W, eps) + activation, the block create_mlp puts between a hidden nn.Linear and the next layer when `ln` is set
+ * (utils/policies/extractors.py:428-430, eps = 1e-3), row-wise over z[M][W] (additions to ABI 11: no existing entry point changed):
+ *   mean = sum z / W, var = sum (z - mean)^2 / W (biased, two passes over registers), rstd = 1 / sqrt(var + eps) (IEEE),
+ *   xhat = (z - mean) rstd, y = act(gamma xhat + beta), act: VF_ACTIVATION_*.
+ * xhat [M][W] and rstd [M] are saved for the backward; xhat may be z itself.  1 <= W <= 512, M >= 1, every leading dimension >= W
+ * (pointers at a column of a wider buffer are fine: columns outside the W are never touched), else VF_EINVAL.  16-byte accesses are
+ * used where W, the row pointers and the leading dimensions are multiples of 4 floats. */
+int vf_layernorm_fwd(const float* z, int32_t ldz, const float* gamma, const float* beta, float eps, float* y, int32_t ldy,
+                     float* xhat, int32_t ldx, float* rstd, int32_t M, int32_t W, int32_t act, vf_stream_t stream);
+/* its backward from the saved y (NULL for act = 0), xhat and rstd: with g = dy act'(y), h = g gamma
+ *   dz = rstd (h - mean_W(h) - xhat mean_W(h xhat));  dgamma (+)= sum_rows g xhat;  dbeta (+)= sum_rows g   (accumulate != 0: +=).
+ * dz may be dy itself.  The sums over rows are deterministic: one partial per wave over a contiguous row range into `scratch`
+ * (vf_layernorm_bwd_scratch_floats(M, W) floats), then a fold in a fixed order; no floating-point atomics. */
+int vf_layernorm_bwd(const float* dy, int32_t lddy, const float* y, int32_t ldy, const float* xhat, int32_t ldx, const float* rstd,
+                     const float* gamma, float* dz, int32_t lddz, float* dgamma, float* dbeta, int32_t M, int32_t W, int32_t act,
+                     int32_t accumulate, float* scratch, vf_stream_t stream);
+int64_t vf_layernorm_bwd_scratch_floats(int32_t M, int32_t W);
+
 /* Whole actor-critic MLP forward in ONE launch (policies.py:195-254: extract_features -> mlp_extractor ->
  * action_net / value_net).  A workgroup walks 64-row tiles; activations live in LDS between layers,
  * the weights come from the packed copy below as the MFMA B operand (two workgroups per CU), fp32 MFMA.

@@ -259,6 +259,11 @@ SIGNATURES = {
     "vf_linear_is_wide": (C.c_int, [C.c_int32, C.c_int32]),
     "vf_linear_bwd_weight": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32,
                                        C.c_int32, _vp, C.c_int32, _vp]),
+    "vf_layernorm_fwd": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_float, _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.c_int32,
+                                   C.c_int32, _vp]),
+    "vf_layernorm_bwd": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "vf_layernorm_bwd_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "vf_episode_stats": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "vf_reparam_fwd": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "vf_reparam_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),

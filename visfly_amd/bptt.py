@@ -136,7 +136,7 @@ class BPTT:
         self._critic_arch = getattr(self, "_critic_arch", None)
         if isinstance(na, dict) and "qf" in na:                       # SB3 get_actor_critic_arch: dict(pi=..., qf=...)
             self._critic_arch = list(na["qf"])
-            pk["net_arch"] = dict(pi=list(na["pi"]), vf=list(na["pi"]))
+            pk["net_arch"] = dict({k: v for k, v in na.items() if k != "qf"}, pi=list(na["pi"]), vf=list(na["pi"]))    # (flags such as pi_ln stay)
         # share_features_extractor=True (td_policies.py:127, SACPolicy._build): the critic runs the ACTOR's extractor under no_grad.  BPTT has
         # no critic (nothing changes); SHAC reads the flag (shac.py: _share_extractor)
         self._share_extractor = bool(pk.pop("share_features_extractor", False))
@@ -166,6 +166,9 @@ class BPTT:
     def _activations(self, pk):
         """(trunk, extractor) VF_ACTIVATION_* of translated policy_kwargs; refuses what this trainer does not run"""
         from .ppo import activation_kind
+        if pk.get("layer_norm"):
+            raise NotImplementedError(f"{type(self).__name__}: layer norm (ln / pi_ln / vf_ln, layer_norm={pk['layer_norm']}) is not implemented: "
+                                      "the horizon kernels have no normalisation step; PPO runs networks with LayerNorm")
         # (native MlpPolicy arguments pass through the translation untouched: there `activation` may be spelt `activation_fn`)
         kinds = activation_kind(pk.get("activation", pk.get("activation_fn", 1))), activation_kind(pk.get("extractor_activation", 1))
         if not self.any_activation:

@@ -4,8 +4,8 @@
   experiment files (exps/examples/alg_cfgs/*/PPO.yaml, env_cfgs/*.yaml; utils/common.py:232-237) are accepted as they
   are; the SB3-style ``policy_kwargs`` (features_extractor_class / features_extractor_kwargs.net_arch.<key>.layer /
   net_arch.pi|vf / activation_fn / optimizer_kwargs) are translated to ``MlpPolicy``'s arguments.  Anything the MFMA
-  policy does not implement (image extractors, batch / layer norm, non-ReLU activations, recurrent extractors)
-  raises instead of being dropped.
+  policy does not implement (image extractors, batch norm, recurrent extractors) raises instead of being dropped;
+  layer norm (``ln`` / ``pi_ln`` / ``vf_ln``) becomes ``MlpPolicy``'s ``layer_norm``.
 * ``policy_state_dict`` / ``load_policy_state_dict``: the flat parameter buffer <-> the parameter names the
   reference's ``CustomMultiInputActorCriticPolicy`` has in its ``state_dict()`` (utils/policies/policies.py:55-190,
   utils/policies/extractors.py:464-486; SB3 2.2.1 ``ActorCriticPolicy``: features_extractor.<key>_extractor.<i>,
@@ -64,11 +64,14 @@ def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dic
     if missing:
         raise ValueError(f"{cls} needs observation keys {missing}")
     arch = (pk.get("features_extractor_kwargs") or {}).get("net_arch") or {}
-    ext = {}
+    # create_mlp (extractors.py:421-430) tests `bn`, then `ln`, by truthiness once for the whole MLP: True or a non-empty list puts
+    # the norm behind every hidden Linear, and bn wins over ln
+    ext, ln_ext = {}, {}
     for k in _EXTRACTORS[cls]:
         a = arch.get(k) or {}
-        if a.get("bn") or a.get("ln"):
-            raise NotImplementedError("batch / layer norm in the extractor MLPs is not implemented")
+        if a.get("bn"):
+            raise NotImplementedError("batch norm in the extractor MLPs is not implemented")
+        ln_ext[k] = bool(a.get("ln"))
         ext[k] = list(a.get("layer", []))
     if arch:        # (no features_extractor_kwargs.net_arch: the trainers' default, the YAMLs' [128, 64] per key)
         out["extractor"] = ext
@@ -86,10 +89,14 @@ def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dic
     na = pk.get("net_arch") or {}
     if isinstance(na, list):        # SB3 shorthand: shared sizes for both trunks
         na = dict(pi=na, vf=na)
-    for flag in ("pi_bn", "pi_ln", "vf_bn", "vf_ln", "squash_output"):
+    for flag in ("pi_bn", "vf_bn", "squash_output"):
         if na.get(flag):
             raise NotImplementedError(f"net_arch.{flag} is not implemented")
     out["pi"], out["vf"] = list(na.get("pi", [64, 64])), list(na.get("vf", [64, 64]))
+    # net_arch.pi_ln / vf_ln (policies.py:34-49) and features_extractor_kwargs.net_arch.<key>.ln -> MlpPolicy's layer_norm; the key
+    # is there only when some MLP is normalised
+    if any(ln_ext.values()) or na.get("pi_ln") or na.get("vf_ln"):
+        out["layer_norm"] = dict(extractor=ln_ext, pi=bool(na.get("pi_ln")), vf=bool(na.get("vf_ln")))
     if "log_std_init" in pk:
         out["log_std_init"] = float(pk["log_std_init"])
     if pk.get("share_features_extractor", True) is False:
@@ -101,7 +108,8 @@ def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dic
 
 
 def _names(policy):
-    """[(layer, reference module prefix)] in schedule order"""
+    """[(layer, reference module prefixes)] in schedule order.  Inside a create_mlp Sequential the i-th Linear is module 2 i (Linear,
+    activation) or, in a normalised MLP, 3 i (Linear, LayerNorm, activation: its LayerNorm is module 3 i + 1, `_ln_prefixes`)"""
     out, idx = [], {}
     for ly in policy.layers:
         if ly.dst in _HEAD_NAMES:
@@ -111,14 +119,19 @@ def _names(policy):
             key = ly.src.split(":")[1] if ly.src.startswith(("obs:", "x:")) else None
             i = idx.get(("ext", key), 0)
             idx[("ext", key)] = i + 1
-            out.append((ly, [f"{p}.{key}_extractor.{2 * i}" for p in ("features_extractor", "pi_features_extractor",
-                                                                        "vf_features_extractor")]))
+            out.append((ly, [f"{p}.{key}_extractor.{(3 if ly.ln else 2) * i}" for p in ("features_extractor", "pi_features_extractor",
+                                                                                         "vf_features_extractor")]))
             continue
         trunk = ly.dst.split(":")[0]
         i = idx.get(trunk, 0)
         idx[trunk] = i + 1
-        out.append((ly, [f"mlp_extractor.{'policy_net' if trunk == 'pi' else 'value_net'}.{2 * i}"]))
+        out.append((ly, [f"mlp_extractor.{'policy_net' if trunk == 'pi' else 'value_net'}.{(3 if ly.ln else 2) * i}"]))
     return out
+
+
+def _ln_prefixes(prefixes):
+    """module names of the nn.LayerNorm behind the Linear named `prefixes`: the next index of the same Sequential"""
+    return [f"{p.rsplit('.', 1)[0]}.{int(p.rsplit('.', 1)[1]) + 1}" for p in prefixes]
 
 
 def policy_state_dict(policy) -> Dict[str, th.Tensor]:
@@ -127,6 +140,10 @@ def policy_state_dict(policy) -> Dict[str, th.Tensor]:
         w, b = policy.weight(ly).detach().cpu().clone(), policy.bias(ly).detach().cpu().clone()
         for p in prefixes:
             sd[p + ".weight"], sd[p + ".bias"] = w, b
+        if ly.ln:
+            g, be = policy.ln_weight(ly).detach().cpu().clone(), policy.ln_bias(ly).detach().cpu().clone()
+            for p in _ln_prefixes(prefixes):
+                sd[p + ".weight"], sd[p + ".bias"] = g, be
     return sd
 
 
@@ -143,6 +160,17 @@ def load_policy_state_dict(policy, sd: Dict[str, th.Tensor], strict: bool = True
             policy.weight(ly).copy_(w.to(policy.device, th.float32))
             policy.bias(ly).copy_(b.to(policy.device, th.float32))
             used.update(q + s for q in prefixes for s in (".weight", ".bias"))
+            if ly.ln:
+                lp = _ln_prefixes(prefixes)
+                q = lp[prefixes.index(p)]
+                if q + ".weight" not in sd or q + ".bias" not in sd:
+                    raise KeyError(f"state_dict has no {q}.weight / .bias (the LayerNorm behind {p})")
+                g, be = sd[q + ".weight"], sd[q + ".bias"]
+                if tuple(g.shape) != (ly.No,) or tuple(be.shape) != (ly.No,):
+                    raise ValueError(f"{q}: shape {tuple(g.shape)} does not match the policy's LayerNorm ({ly.No},)")
+                policy.ln_weight(ly).copy_(g.to(policy.device, th.float32))
+                policy.ln_bias(ly).copy_(be.to(policy.device, th.float32))
+                used.update(r + s for r in lp for s in (".weight", ".bias"))
         if "log_std" in sd:
             policy.log_std.copy_(sd["log_std"].to(policy.device, th.float32).reshape(-1))
             used.add("log_std")
@@ -164,6 +192,8 @@ def _param_order(policy):
                         2 if pre.startswith("mlp_extractor.value") else 3 if pre == "action_net" else 4)
     for ly, prefixes in sorted(named, key=lambda x: rank(x[1][0])):
         order += [(ly.w_off, (ly.No, ly.K)), (ly.b_off, (ly.No,))]
+        if ly.ln:          # the LayerNorm is registered right behind its Linear: weight, bias
+            order += [(ly.g_off, (ly.No,)), (ly.be_off, (ly.No,))]
     return order
 
 
@@ -185,6 +215,27 @@ def check_activations(policy, spec):
         raise ValueError(f"the archive holds a network with activations {spec.get('activation', 'relu')} (trunks) / "
                          f"{spec.get('extractor_activation', 'relu')} (extractor), this trainer's policy has {have['activation']} / "
                          f"{have['extractor_activation']}: pass the archive's activation_fn (or use load(), which reads it)")
+
+
+def layer_norm_spec(spec) -> dict:
+    """the `layer_norm` entry of a policy spec with every flag spelled out; a spec without it (every archive written before LayerNorm,
+    every network without it) is all false"""
+    spec = spec if isinstance(spec, dict) else {}
+    ln = spec.get("layer_norm") or {}
+    return dict(extractor={k: bool((ln.get("extractor") or {}).get(k, False)) for k in spec.get("extractor", {})},
+                pi=bool(ln.get("pi", False)), vf=bool(ln.get("vf", False)))
+
+
+def check_layer_norm(policy, spec):
+    """like check_activations: weights trained with (without) LayerNorm must not run without (with) it.  ValueError when the archive's
+    spec and the policy disagree about which MLPs are normalised"""
+    if not isinstance(spec, dict) or "extractor" not in spec:
+        return
+    want, have = layer_norm_spec(spec), layer_norm_spec(policy.spec)
+    if (want["pi"], want["vf"], sorted(k for k, v in want["extractor"].items() if v)) != \
+            (have["pi"], have["vf"], sorted(k for k, v in have["extractor"].items() if v)):
+        raise ValueError(f"the archive holds a network with layer_norm {want}, this trainer's policy has {have}: pass the archive's "
+                         "ln / pi_ln / vf_ln flags (or use load(), which reads them)")
 
 
 def _hyper(trainer) -> dict:
@@ -267,6 +318,8 @@ def ctor_kwargs_from_archive(path: str, overrides: Optional[dict] = None) -> dic
         if isinstance(spec, dict) and "extractor" in spec:
             kw["policy_kwargs"] = dict(extractor=spec["extractor"], pi=spec["pi"], vf=spec["vf"], activation=spec.get("activation", "relu"),
                                        extractor_activation=spec.get("extractor_activation", "relu"))
+            if spec.get("layer_norm"):
+                kw["policy_kwargs"]["layer_norm"] = spec["layer_norm"]
     kw.update(overrides or {})
     return kw
 
@@ -278,6 +331,8 @@ def load_into(trainer, path: str, load_optimizer: bool = True):
     pol = trainer.policy
     if hasattr(trainer, "any_activation") and isinstance(data, dict):      # BPTT / SHAC archives (see _hyper)
         check_activations(pol, data.get("policy_spec"))
+    if isinstance(data, dict):
+        check_layer_norm(pol, data.get("policy_spec"))
     load_policy_state_dict(pol, sd, strict=True)
     if load_optimizer and opt and opt.get("state"):
         order = _param_order(pol)

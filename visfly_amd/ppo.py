@@ -35,6 +35,9 @@ _TORCH_ACT = {1: "ReLU", 2: "Tanh", 3: "ELU", 4: "LeakyReLU"}
 # weight_grad_slots: rows per weight-gradient launch of a horizon (profiles/r06_bptt_wgrad_chunks.txt)
 WGRAD_SPLIT_ROWS = 524288
 
+# nn.LayerNorm's eps in create_mlp (utils/policies/extractors.py:429)
+LN_EPS = 1e-3
+
 # widest layer (in or out) of an MlpPolicy: the per-layer kernels' limit (vf_linear_*: K, No <= 512) / of a network the one-launch,
 # register-chained and persistent kernels can run (K, No <= 128: vf_linear_is_wide)
 MAX_WIDTH, FUSED_MAX_WIDTH = 512, 128
@@ -62,6 +65,9 @@ class _Linear:
         self.src, self.sc, self.dst, self.dc = src, sc, dst, dc
         self.w_off, self.b_off, self.first = w_off, b_off, first
         self.frozen = False       # identity pass-through (MlpPolicy ``passthrough``): no gradient, not in the backward tables
+        # nn.LayerNorm(No, eps=1e-3) between the Linear and its activation (create_mlp's ``ln``): gamma / beta sit right behind the
+        # layer's own bias in ``flat`` (g_off, be_off); ``ln_key`` names the layer's pre-norm / rstd buffers
+        self.ln, self.g_off, self.be_off, self.ln_key = False, None, None, None
 
 
 class MlpPolicy:
@@ -76,7 +82,8 @@ class MlpPolicy:
 
     def __init__(self, obs_dims: Dict[str, int], extractor: Dict[str, List[int]], pi: List[int], vf: List[int],
                  device, action_dim: int = 4, log_std_init: float = 0.0, seed: int = 0, ortho_init: bool = True,
-                 head_dims=None, passthrough=(), log_std_param: bool = True, activation="relu", extractor_activation="relu"):
+                 head_dims=None, passthrough=(), log_std_param: bool = True, activation="relu", extractor_activation="relu",
+                 layer_norm=None):
         """``head_dims`` (default (action_dim, 1)): widths of the two heads "mean" / "value" -- the SHAC actor of the reference
         has two 4-wide heads (mu and a state-dependent log_std, utils/policies/td_policies.py:230-243), its twin critic two
         1-wide ones.  ``passthrough``: input keys whose columns are appended to the features unchanged, after the extractor
@@ -87,7 +94,13 @@ class MlpPolicy:
         policies.py:108: the reference's default there is Tanh) and of the extractor MLPs (``features_extractor_kwargs.activation_fn``,
         extractors.py:560,583: default ReLU): relu | tanh | elu | leaky_relu.  The register-chained classes built into the library are
         ReLU networks; for another activation the class is generated and compiled on first use like a non-default net_arch
-        (visfly_amd/_jit.py: the activation is part of the class), else the block-tile kernels run it."""
+        (visfly_amd/_jit.py: the activation is part of the class), else the block-tile kernels run it.
+        ``layer_norm``: dict(extractor={key: bool}, pi=bool, vf=bool) -- create_mlp's ``ln`` (extractors.py:428-430; the YAMLs'
+        features_extractor_kwargs.net_arch.<key>.ln and net_arch.pi_ln / vf_ln): nn.LayerNorm(width, eps=1e-3) between every hidden
+        Linear of that MLP and its activation; the heads are never normalised.  gamma (ones) and beta (zeros) follow the layer's own
+        weight and bias in ``flat``: W, b, gamma, beta.  Such a network has no fused plan: it runs layer by layer on vf_linear_* with
+        vf_layernorm_* in between (csrc/vf_layernorm.hip).  None / all flags false: the network, its parameter layout and its path
+        are exactly what they are without the argument."""
         assert action_dim == 4, "the head kernels are written for the 4-d drone action"
         self.device = th.device(device)
         self.passthrough = [k for k in passthrough]
@@ -99,15 +112,28 @@ class MlpPolicy:
         if (self.act, self.ext_act) != (1, 1):        # (archives of ReLU networks keep the r05 spec)
             self.spec.update(activation=_TORCH_ACT[self.act].lower().replace("leakyrelu", "leaky_relu"),
                              extractor_activation=_TORCH_ACT[self.ext_act].lower().replace("leakyrelu", "leaky_relu"))
+        ln = dict(layer_norm or {})
+        unknown = set(ln) - {"extractor", "pi", "vf"} | set(ln.get("extractor") or {}) - set(extractor)
+        if unknown:
+            raise ValueError(f"layer_norm: unknown entries {sorted(unknown)} (dict(extractor={{key: bool}}, pi=bool, vf=bool))")
+        ln_ext = {k: bool((ln.get("extractor") or {}).get(k, False)) for k in extractor}
+        ln_trunk = {"pi": bool(ln.get("pi", False)), "vf": bool(ln.get("vf", False))}
+        self.ln = any(ln_ext.values()) or any(ln_trunk.values())
+        if self.ln:                                   # (archives of networks without LayerNorm keep their spec)
+            self.spec["layer_norm"] = dict(extractor=ln_ext, pi=ln_trunk["pi"], vf=ln_trunk["vf"])
         # ---- activation buffers (name -> width) and the layer schedule ----
         self.widths: Dict[str, int] = {}
         self.layers: List[_Linear] = []
         off = 0
 
-        def add(K, No, relu, src, sc, dst, dc, first=False):
+        def add(K, No, relu, src, sc, dst, dc, first=False, ln=False):
             nonlocal off
             self.layers.append(_Linear(K, No, relu, src, sc, dst, dc, off, off + K * No, first))
             off += K * No + No
+            if ln:
+                ly = self.layers[-1]
+                ly.ln, ly.g_off, ly.be_off, ly.ln_key = True, off, off + No, f"{dst}:{dc}"
+                off += 2 * No
 
         feat_w = sum((v[-1] if v else self.obs_dims[k]) for k, v in extractor.items()) + sum(self.obs_dims[k] for k in self.passthrough)
         self.widths["feat"] = feat_w
@@ -122,7 +148,7 @@ class MlpPolicy:
                 dc = col if last else 0
                 if not last:
                     self.widths[dst] = h
-                add(K, h, self.ext_act, src, sc, dst, dc, first=(li == 0))
+                add(K, h, self.ext_act, src, sc, dst, dc, first=(li == 0), ln=ln_ext[k])
                 src, sc, K = dst, dc, h
             col += hidden[-1]
         pass_cols = []
@@ -134,7 +160,7 @@ class MlpPolicy:
             for li, h in enumerate(hidden):
                 dst = f"{trunk}:{li}"
                 self.widths[dst] = h
-                add(K, h, self.act, src, sc, dst, 0)
+                add(K, h, self.act, src, sc, dst, 0, ln=ln_trunk[trunk])
                 src, sc, K = dst, 0, h
             self.widths[head] = head_dim
             add(K, head_dim, 0, src, sc, head, 0)
@@ -166,6 +192,8 @@ class MlpPolicy:
             if ly.frozen:
                 flat[ly.w_off:ly.w_off + ly.K * ly.No] = th.eye(ly.K).reshape(-1)
                 continue
+            if ly.ln:        # nn.LayerNorm's own initialisation; SB3's orthogonal init touches nn.Linear only
+                flat[ly.g_off:ly.g_off + ly.No] = 1.0
             if ortho_init:
                 gain = {"mean": 0.01, "value": 1.0}.get(ly.dst, float(np.sqrt(2.0)))
                 w = th.empty(ly.No, ly.K)
@@ -185,7 +213,9 @@ class MlpPolicy:
         # instead of a resident weight matrix (csrc/vf_linear_wide.hip); the one-launch kernels, the chain classes and the persistent
         # horizons stop at 128, so such a network has no plan and runs layer by layer like one with too many buffers
         self.wide = any(ly.K > FUSED_MAX_WIDTH or ly.No > FUSED_MAX_WIDTH for ly in self.layers)
-        self._plan = None if self.wide else self._plan_fused()
+        # LayerNorm (``self.ln``): the one-launch, chain and persistent kernels have no normalisation step -- no plan either, the
+        # layers run one by one with vf_layernorm_fwd / _bwd between them
+        self._plan = None if (self.wide or self.ln) else self._plan_fused()
         self._descs = {}
         # chain kernels of a shape the library holds no instance of: compiled on first use (visfly_amd/_jit.py)
         # (heads (4, 1) with the log_std parameter: the PPO policies' actor-critic; (4, 4) without: the SAC-style Actor of BPTT / SHAC;
@@ -221,6 +251,11 @@ class MlpPolicy:
         if not getattr(self, "_warned_fallback", False):
             self._warned_fallback = True
             import warnings
+            if self.ln:
+                warnings.warn(f"visfly_amd: {what}: this network has layer norm (nn.LayerNorm in {self.spec['layer_norm']}); networks "
+                              "with LayerNorm run layer by layer on the per-layer MFMA linear kernels with the row-wise LayerNorm "
+                              "kernels in between -- no one-launch, register-chained or persistent path", stacklevel=3)
+                return
             if self.wide:
                 warnings.warn(f"visfly_amd: {what}: this network has layers wider than {FUSED_MAX_WIDTH} "
                               f"(extractor {self.spec['extractor']}, pi {self.spec['pi']}, vf {self.spec['vf']}); they run layer by layer "
@@ -379,6 +414,12 @@ class MlpPolicy:
     def bias(self, ly):
         return self.flat[ly.b_off:ly.b_off + ly.No]
 
+    def ln_weight(self, ly):
+        return self.flat[ly.g_off:ly.g_off + ly.No]
+
+    def ln_bias(self, ly):
+        return self.flat[ly.be_off:ly.be_off + ly.No]
+
     @property
     def log_std(self):
         return self.flat[self.log_std_off:self.n_params]
@@ -395,6 +436,10 @@ class MlpPolicy:
                 self._descs.clear()
                 self._slot_blocks.clear()
             b = {name: th.empty((M, w), dtype=th.float32, device=self.device) for name, w in self.widths.items()}
+            for ly in self.layers:
+                if ly.ln:     # the Linear's output, overwritten by xhat (what the backward needs), and 1 / sqrt(var + eps) per row
+                    b["z:" + ly.ln_key] = th.empty((M, ly.No), dtype=th.float32, device=self.device)
+                    b["r:" + ly.ln_key] = th.empty(M, dtype=th.float32, device=self.device)
             g = self._gbufs.get(M)
             if g is None:
                 g = self._gbufs[M] = {"g:" + name: th.empty((M, w), dtype=th.float32, device=self.device)
@@ -407,6 +452,8 @@ class MlpPolicy:
         """activation / gradient buffers of slots 0..n-1 stored back to back per buffer ([n][M][w]), observations
         copied in: the rows of all slots then form ONE (n M, w) matrix per buffer, which is what lets
         ``weight_grad_slots`` reduce the weight gradient of a whole BPTT horizon in one launch"""
+        if self.ln:
+            raise NotImplementedError("layer norm: the horizon paths (reserved slots) are not implemented for networks with LayerNorm")
         if self._slot_blocks.get(M, (0,))[0] >= n:
             return
         for key in [k for k in self._bufs if k[0] == M]:
@@ -461,10 +508,20 @@ class MlpPolicy:
             if rc:
                 _lib.check(rc)
             return b["mean"], (vout if need_value else None)
-        if self.wide:
+        if self.wide or self.ln:
             self._warn_fallback("forward")
         for ly in self.layers:
             X, Y = b[ly.src], b[ly.dst]
+            if ly.ln:        # Linear into the pre-norm buffer, then LayerNorm + activation into the destination (xhat replaces z)
+                Z = b["z:" + ly.ln_key]
+                rc = L.vf_linear_fwd(_ptr(X, ly.sc), X.shape[1], _ptr(self.flat, ly.w_off), _ptr(self.flat, ly.b_off),
+                                     _ptr(Z), ly.No, M, ly.K, ly.No, 0, st)
+                rc = rc or L.vf_layernorm_fwd(_ptr(Z), ly.No, _ptr(self.flat, ly.g_off), _ptr(self.flat, ly.be_off), LN_EPS,
+                                              _ptr(Y, ly.dc), Y.shape[1], _ptr(Z), ly.No, _ptr(b["r:" + ly.ln_key]), M, ly.No,
+                                              int(ly.relu), st)
+                if rc:
+                    _lib.check(rc)
+                continue
             rc = L.vf_linear_fwd(_ptr(X, ly.sc), X.shape[1], _ptr(self.flat, ly.w_off), _ptr(self.flat, ly.b_off),
                                  _ptr(Y, ly.dc), Y.shape[1], M, ly.K, ly.No, int(ly.relu), st)
             if rc:
@@ -485,7 +542,8 @@ class MlpPolicy:
         L, st = _lib.lib(), self._stream()
         if self.fused_backward and self._plan is not None:
             return self._backward_fused(b, M, d_mean, d_value, d_log_std, accumulate, need_input_grad)
-        need = max(int(L.vf_linear_bwd_scratch_floats(M, ly.K, ly.No)) for ly in self.layers)
+        need = max(max(int(L.vf_linear_bwd_scratch_floats(M, ly.K, ly.No)), int(L.vf_layernorm_bwd_scratch_floats(M, ly.No)) if ly.ln else 0)
+                   for ly in self.layers)
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = th.empty(need, dtype=th.float32, device=self.device)
         gbuf = {} if d_mean is None else {"mean": d_mean}
@@ -504,8 +562,20 @@ class MlpPolicy:
             dY = gbuf.get(ly.dst, b.get("g:" + ly.dst))
             Y, X = b[ly.dst], b[ly.src]
             ym = _ptr(Y, ly.dc) if ly.relu else None
+            act = int(ly.relu)
+            if ly.ln:
+                # through activation and LayerNorm first: dY becomes the gradient of the Linear's own output (in place: this layer is
+                # the only reader of its slice of the g: buffer), dgamma / dbeta go straight into the flat gradient; the Linear's
+                # three products then see a layer without activation
+                rc = L.vf_layernorm_bwd(_ptr(dY, ly.dc), dY.shape[1], ym, Y.shape[1], _ptr(b["z:" + ly.ln_key]), ly.No,
+                                        _ptr(b["r:" + ly.ln_key]), _ptr(self.flat, ly.g_off), _ptr(dY, ly.dc), dY.shape[1],
+                                        _ptr(self.grad, ly.g_off), _ptr(self.grad, ly.be_off), M, ly.No, act, 1 if accumulate else 0,
+                                        _ptr(self._scratch), st)
+                if rc:
+                    _lib.check(rc)
+                ym, act = None, 0
             rc = wgrad(_ptr(dY, ly.dc), dY.shape[1], ym, Y.shape[1], _ptr(X, ly.sc), X.shape[1],
-                       _ptr(self.grad, ly.w_off), _ptr(self.grad, ly.b_off), M, ly.K, ly.No, _ptr(self._scratch), int(ly.relu), st)
+                       _ptr(self.grad, ly.w_off), _ptr(self.grad, ly.b_off), M, ly.K, ly.No, _ptr(self._scratch), act, st)
             if rc:
                 _lib.check(rc)
             if ly.first and not need_input_grad:
@@ -516,7 +586,7 @@ class MlpPolicy:
                 dX = b["g:" + ly.src]
             key = (ly.src, ly.sc)
             rc = L.vf_linear_bwd_data(_ptr(dY, ly.dc), dY.shape[1], ym, Y.shape[1], _ptr(self.flat, ly.w_off),
-                                      _ptr(dX, ly.sc), dX.shape[1], M, ly.K, ly.No, 1 if key in touched else 0, int(ly.relu), st)
+                                      _ptr(dX, ly.sc), dX.shape[1], M, ly.K, ly.No, 1 if key in touched else 0, act, st)
             if rc:
                 _lib.check(rc)
             touched.add(key)
@@ -879,19 +949,27 @@ class MlpPolicy:
             def __init__(s):
                 super().__init__()
                 s.lin = nn.ModuleList()
-                for ly in pol.layers:
+                s.norm = nn.ModuleDict()        # str(index into pol.layers) -> that layer's nn.LayerNorm; `lin` still zips with pol.layers
+                for i, ly in enumerate(pol.layers):
                     m = nn.Linear(ly.K, ly.No)
                     m.weight.data.copy_(pol.weight(ly).cpu())
                     m.bias.data.copy_(pol.bias(ly).cpu())
                     s.lin.append(m)
+                    if ly.ln:
+                        n = nn.LayerNorm(ly.No, eps=LN_EPS)
+                        n.weight.data.copy_(pol.ln_weight(ly).cpu())
+                        n.bias.data.copy_(pol.ln_bias(ly).cpu())
+                        s.norm[str(i)] = n
                 s.log_std = nn.Parameter(pol.log_std.detach().cpu().clone())
 
             def forward(s, obs):
                 acts = {"obs:" + k: v for k, v in obs.items()}
                 M = next(iter(obs.values())).shape[0]
-                for ly, m in zip(pol.layers, s.lin):
+                for i, (ly, m) in enumerate(zip(pol.layers, s.lin)):
                     x = acts[ly.src][:, ly.sc:ly.sc + ly.K]
                     y = m(x)
+                    if ly.ln:
+                        y = s.norm[str(i)](y)
                     y = getattr(nn, _TORCH_ACT[ly.relu])()(y) if ly.relu else y
                     if ly.dst == "feat":
                         if "feat" not in acts:
@@ -899,15 +977,19 @@ class MlpPolicy:
                         acts["feat"] = th.cat([acts["feat"][:, :ly.dc], y, acts["feat"][:, ly.dc + ly.No:]], dim=1)
                     else:
                         acts[ly.dst] = y
+                s.acts = acts                   # the last pass's layer outputs by buffer name (tests read the trunks' from here)
                 return acts["mean"], acts["value"]
 
             def flat_grad(s):
                 g = th.zeros(pol.n_params)
-                for ly, m in zip(pol.layers, s.lin):
+                for i, (ly, m) in enumerate(zip(pol.layers, s.lin)):
                     if ly.frozen or m.weight.grad is None:
                         continue
                     g[ly.w_off:ly.w_off + ly.K * ly.No] = m.weight.grad.reshape(-1)
                     g[ly.b_off:ly.b_off + ly.No] = m.bias.grad
+                    if ly.ln:
+                        g[ly.g_off:ly.g_off + ly.No] = s.norm[str(i)].weight.grad
+                        g[ly.be_off:ly.be_off + ly.No] = s.norm[str(i)].bias.grad
                 if s.log_std.grad is not None and pol.n_params > pol.log_std_off:
                     g[pol.log_std_off:] = s.log_std.grad
                 return g
@@ -970,7 +1052,10 @@ class PPO:
         extractor = pk.get("extractor", {k: [128, 64] for k in self.obs_keys})
         self.policy = MlpPolicy(obs_dims, extractor, pk.get("pi", [64, 64]), pk.get("vf", [64, 64]), self.device,
                                 log_std_init=pk.get("log_std_init", 0.0), seed=seed, ortho_init=pk.get("ortho_init", True),
-                                activation=pk.get("activation", "relu"), extractor_activation=pk.get("extractor_activation", "relu"))
+                                activation=pk.get("activation", "relu"), extractor_activation=pk.get("extractor_activation", "relu"),
+                                layer_norm=pk.get("layer_norm"))
+        if self.policy.ln:
+            self.policy._warn_fallback("PPO")
         self.policy.lazy_pack = True        # this trainer calls mark_updated() after every optimiser step
         self.world, self.rank = parallel.world_size(), parallel.rank()
         # every rank must start from the SAME parameters (only gradients are exchanged afterwards) and draw DIFFERENT
