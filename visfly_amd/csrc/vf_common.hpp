@@ -66,13 +66,14 @@ inline bool use_split(int agents_padded, const vf_dyn_cfg& cfg)
 struct vf_env_dev {
     vf_env_cfg cfg;
     unsigned agent0;   // global id of the handle's first agent (vf_env_set_agent_offset): the Philox counter word of row i is agent0 + i
-    unsigned pad;
+    float hit_y;       // hit_threshold(cfg.uav_radius) (vf_step_consts.hpp): `y < hit_y` is `sqrtf(y) < uav_radius` for every y
 };
 
 #ifdef __HIPCC__
 // `e` must be the handle's device block (what the step / roll-out kernels get through their pointer argument), NOT a by-value copy
 // of a vf_env_cfg: k_env_reset takes the value in its argument struct instead
 __device__ __forceinline__ unsigned env_agent0(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_dev&>(e).agent0; }
+__device__ __forceinline__ float env_hit_y(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_dev&>(e).hit_y; }
 
 // ---- wave64 reductions: fixed shuffle tree, the sum lands in lane 0 ----
 __device__ __forceinline__ double wave_sum(double x)

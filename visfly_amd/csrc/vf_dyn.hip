@@ -223,7 +223,7 @@ int vf_dyn_create(const vf_dyn_cfg* cfg, int32_t N, int32_t per_agent_drag, vf_d
     if (int rc = vf::check_dyn_cfg(cfg)) return rc;
     vf_dyn* h = new vf_dyn;
     vf::init_dyn_handle(h, cfg, N, per_agent_drag, 0);
-    if (int rc = vf::upload_cfg(h->cfg, &h->d_cfg)) {
+    if (int rc = vf::upload_dyn_dev(h->cfg, &h->d_cfg)) {
         delete h;
         return rc;
     }

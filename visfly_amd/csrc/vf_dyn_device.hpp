@@ -14,6 +14,7 @@
 
 #include "vf_common.hpp"
 #include "vf_pair_algebra.hpp"
+#include "vf_step_consts.hpp"
 #include "vf_xmath.hpp"
 #include "visfly_amd.h"
 
@@ -65,6 +66,61 @@ __device__ __forceinline__ IntervalMats interval_mats(const vf_dyn_cfg& c)
 {
     return IntervalMats{mat4_pairs(c.B), mat3_pairs(c.J), mat3_pairs(c.Jinv), rotor_k(c)};
 }
+
+// Where a control interval takes its matrices from, and how it takes the rotor set-points' square roots: the default is today's code
+// (scalar loads of vf_dyn_cfg moved into VGPR pairs; one sqrtf per rotor)
+struct MatsOfCfg {
+    static constexpr bool paired_sqrt = false;
+    __device__ __forceinline__ IntervalMats operator()(const vf_dyn_cfg& c) const { return interval_mats(c); }
+};
+// ... from the packed block behind the device copy of vf_dyn_cfg (vf_step_consts.hpp), fetched with eight 16-byte VECTOR loads of a
+// lane-uniform address straight into the pairs: issued with the first burst of state loads, they cost eight issue slots instead of a
+// scalar load, a wait and a v_mov per word.  The address is uniform, and the compiler would turn the loads into scalar ones if it could
+// see that: the zero offset comes out of an asm statement.
+struct StepConstsV {
+    float4 v[8];
+};
+__device__ __forceinline__ StepConstsV load_step_consts(const vf_dyn_cfg* cp)
+{
+    unsigned z;
+    asm("v_mov_b32 %0, 0" : "=v"(z));
+    const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(cp) + kStepConstsOffset + z);
+    StepConstsV k;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k.v[j] = p[j];
+    return k;
+}
+struct MatsOfBlock {
+    static constexpr bool paired_sqrt = true;
+    StepConstsV k;
+    __device__ __forceinline__ IntervalMats operator()(const vf_dyn_cfg& c) const
+    {
+        IntervalMats M;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            M.B.c01[j] = pair_of(k.v[j].x, k.v[j].y);
+            M.B.c23[j] = pair_of(k.v[j].z, k.v[j].w);
+        }
+        const vf_f2 h[8] = {pair_of(k.v[4].x, k.v[4].y), pair_of(k.v[4].z, k.v[4].w), pair_of(k.v[5].x, k.v[5].y), pair_of(k.v[5].z, k.v[5].w),
+                            pair_of(k.v[6].x, k.v[6].y), pair_of(k.v[6].z, k.v[6].w), pair_of(k.v[7].x, k.v[7].y), pair_of(k.v[7].z, k.v[7].w)};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            M.J.r0[j] = c.J[j];
+            M.Jinv.r0[j] = c.Jinv[j];
+            M.J.c12[j] = h[j];
+            M.Jinv.c12[j] = h[3 + j];
+        }
+        M.k.K0 = h[6];
+        M.k.K1 = h[7];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { keep_in_vgprs(M.B.c01[j]); keep_in_vgprs(M.B.c23[j]); }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { keep_in_vgprs(M.J.c12[j]); keep_in_vgprs(M.Jinv.c12[j]); }
+        keep_in_vgprs(M.k.K0);
+        keep_in_vgprs(M.k.K1);
+        return M;
+    }
+};
 
 // a 3-vector as the mat3_p results come: component 0 by itself, (1, 2) as a pair
 struct Vec3P {
@@ -258,10 +314,20 @@ __device__ __forceinline__ void desired_thrusts(const vf_dyn_cfg& c, const Agent
 
 // rotor set-point contribution (1 - c) * omega_des: loop invariant (thrust_des is fixed for the
 // interval), so the quadratic root of dynamics.py:545-553 is taken once, not once per sub-step.
-template <bool CTRL_DELAY>
+// PAIRED: the four square roots as sqrt_p2 (vf_pair_algebra.hpp), the same operations
+template <bool CTRL_DELAY, bool PAIRED = false>
 __device__ __forceinline__ void rotor_setpoint(const vf_dyn_cfg& c, const float* Td, float* wd)
 {
-    if constexpr (CTRL_DELAY) {
+    if constexpr (CTRL_DELAY && PAIRED) {
+        float d3[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d3[k] = c.rot_tm1sq - c.rot_4tm0 * (c.tm2 - Td[k]);
+        vf_f2 r01, r23;
+        sqrt_p2(pair_of(d3[0], d3[1]), pair_of(d3[2], d3[3]), r01, r23);
+        const float r[4] = {r01[0], r01[1], r23[0], r23[1]};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wd[k] = (c.one_minus_c) * (c.rot_scale * (c.rot_neg_tm1 + r[k]));
+    } else if constexpr (CTRL_DELAY) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float d3 = c.rot_tm1sq - c.rot_4tm0 * (c.tm2 - Td[k]);
@@ -571,15 +637,17 @@ __device__ __forceinline__ void control_interval(const vf_dyn_cfg& c, Agent& s, 
 
 // control_interval with the sub-step loop on register pairs (vf_pair_algebra.hpp): the single-step kernels of vf_env.hip / vf_dyn.hip.
 // Bit-identical to control_interval (same IEEE operations in the same order).
-template <int ACT, int INTEG, bool CTRL_DELAY, class CK = NoCheckpoint>
+// MF: the source of the interval's matrices (MatsOfCfg, MatsOfBlock)
+template <int ACT, int INTEG, bool CTRL_DELAY, class CK = NoCheckpoint, class MF = MatsOfCfg>
 __device__ __forceinline__ void control_interval_pairs(const vf_dyn_cfg& c, Agent& s, const float* a,
-                                                 const float* kl, const float* kq, bool vstrided = false, const CK& ck = CK{})
+                                                 const float* kl, const float* kq, bool vstrided = false, const CK& ck = CK{},
+                                                 const MF& mf = MF{})
 {
     float Td[4], wd[4];
     desired_thrusts<ACT>(c, s, a, Td, vstrided);
-    rotor_setpoint<CTRL_DELAY>(c, Td, wd);
+    rotor_setpoint<CTRL_DELAY, MF::paired_sqrt>(c, Td, wd);
     // the rotational state and the rotors live on register pairs through the loop (vf_pair_algebra.hpp), converted before and after it
-    const IntervalMats M = interval_mats(c);
+    const IntervalMats M = mf(c);
     RotorsP r(s, Td, wd);
     QuatP q = to_pairs(s.q), wq{pair_of(0.0f, s.w[0]), pair_of(s.w[1], s.w[2])};
     const auto mirror = [&] {

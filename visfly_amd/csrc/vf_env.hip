@@ -39,7 +39,15 @@ namespace vf {
 // Everything the first burst of loads needs (slab, action rows, N, G, ring slot, drag granule) is among them, so the burst is issued without a single scalar-memory round trip;
 // the rest of the kernel arguments and the two constant blocks arrive, in ONE batch, while it is in flight.  Before: kernel arguments
 // (0.4 us), then the constant block for delay_steps (0.4 us), then the loads (timeline: profiles/r04_env_timeline.txt).
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool LAZY_SLOT = false>
+//
+// STRAIGHT: the launch-uniform options of the common configuration decided on the host (pick_env_kernel) instead of in every wave: no
+// per-agent drag granules, no wind rows, no done list, no stale bits, raw observation rows, auto_reset with the prefetched re-spawn
+// (helper blocks behind the main ones), eager slot loads.  The fields of the local EnvArgs copy that those options fix are overwritten
+// with their known values, so every branch on them in the shared device functions folds away with its predicate, its phi copies and
+// the loads behind its untaken arm; the arithmetic is the same code.  What depends on data, on N or on a pointer's alignment stays:
+// the episode-end block, the re-spawn, the optional episode outputs behind `if (done)`, the partial / unaligned store path, the delay
+// ring (delay_steps is a preloaded scalar) and is_collision_reset.  profiles/env_straight_line.txt
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool LAZY_SLOT = false, bool STRAIGHT = false>
 __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, float* S,
                                                      const float4* action, int N, int G, int head, int helper, int delay_steps,
                                                      int g_drag, const EnvArgs g0)
@@ -49,6 +57,14 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
     __shared__ __attribute__((aligned(16))) float tile[kBlock * 13];
     EnvArgs g = g0;
     g.d.S = S; g.d.action = action; g.d.N = N; g.d.G = G; g.d.head = head; g.helper = helper; g.d.g_drag = g_drag;
+    if constexpr (STRAIGHT) {
+        static_assert(!LAZY_SLOT, "the straight-line instance loads the spawn slot eagerly");
+        g.d.g_drag = -1; g.d.wind = nullptr;
+        g.out.done_list = nullptr; g.out.done_count = nullptr;
+        g.stale = nullptr; g.auto_reset = 1;
+        __builtin_assume(g.helper > 0);
+        __builtin_assume(g.g_spawn_rd >= 0);
+    }
     // the blocks behind the g.helper main blocks: helper blocks (prefetched re-spawn), kHelperSpan agents per thread (a workgroup dispatch
     // costs more than their checks).  (Laying the helper's code and the episode-end blocks out behind the hot path with __builtin_expect --
     // the instruction cache is cold at every launch -- was measured in both regimes: no difference, profiles/r04_env_timeline.txt)
@@ -72,6 +88,8 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
     load_agent<false>(g.d.S, g.d.G, i, s, sp);
     float4 dk0 = make_float4(0.f, 0.f, 0.f, 0.f), dk1 = dk0;
     if (g.d.g_drag >= 0) { dk0 = *granule(g.d.S, g.d.G, i, g.d.g_drag); dk1 = *granule(g.d.S, g.d.G, i, g.d.g_drag + 1); }
+    StepConstsV kv;          // the loop's matrices, with the burst (MatsOfBlock)
+    if constexpr (STRAIGHT) kv = load_step_consts(cp);
     // ... and behind the burst ONE batch of scalar loads: the remaining kernel-argument lines and the lines of the two constant blocks
     // (first touched one after the other on the way, each was a round trip a lone wave sits out in full)
 #ifdef VF_ENV_TRACE
@@ -93,6 +111,11 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
 #pragma unroll
         for (int k = 0; k < 3; ++k) { kl[k] = c.k_lin[k]; kq[k] = c.k_quad[k]; }
     }
+    // The wind and the drag coefficients are wave-uniform here.  Left in SGPRs they change the sub-step loop's schedule for the worse (251
+    // issue slots instead of 248: pads behind the loop's square root, profiles/env_straight_line.txt); in VGPRs, where the general kernel
+    // has them (wind rows, drag granules), they cost nine moves in front of the loop
+    if constexpr (STRAIGHT)
+        asm("" : "+v"(s.wnd[0]), "+v"(s.wnd[1]), "+v"(s.wnd[2]), "+v"(kl[0]), "+v"(kl[1]), "+v"(kl[2]), "+v"(kq[0]), "+v"(kq[1]), "+v"(kq[2]));
 #ifdef VF_ENV_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     VF_TR(4);                                        // loads arrived
@@ -108,11 +131,14 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
     asm volatile("" :: "v"(s.p[0]), "v"(s.q.w), "v"(s.v[0]), "v"(s.w[0]) : "memory");
     VF_TR(7);                                        // interval done
 #else
-    control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
+    if constexpr (STRAIGHT)
+        control_interval_pairs<ACT, INTEG, CTRL_DELAY, NoCheckpoint, MatsOfBlock>(c, s, a, kl, kq, g.d.vstrided != 0, NoCheckpoint{}, MatsOfBlock{kv});
+    else
+        control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
 #endif
     const int wave = threadIdx.x >> 6;
 #ifdef VF_ENV_TRACE
-    env_epilogue<KIND, true, 1, false, LAZY_SLOT>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13, nullptr, nullptr, tr);
+    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13, nullptr, nullptr, tr);
     asm volatile("" ::: "memory");
     VF_TR(11);                                       // stores issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -131,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
         }
     }
 #else
-    env_epilogue<KIND, true, 1, false, LAZY_SLOT>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
+    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
 #endif
 }
 
@@ -446,9 +472,29 @@ EnvStepKernel pick_env_split(const vf_env* h)
 }
 
 
-EnvStepKernel pick_env_kernel(const vf_env* h)
+// the straight-line instances of k_env_step (STRAIGHT): the hover and navigation kinds under the body-rate controller, both integrators,
+// with and without the motor lag
+template <int KIND>
+EnvStepKernel pick_env_straight_k(const vf_dyn_cfg& c)
+{
+    const int key = (c.integrator == VF_INT_RK4 ? 2 : 0) | (c.ctrl_delay ? 1 : 0);
+    switch (key) {
+    case 0: return vf::k_env_step<KIND, VF_ACT_BODYRATE, VF_INT_EULER, false, false, true>;
+    case 1: return vf::k_env_step<KIND, VF_ACT_BODYRATE, VF_INT_EULER, true, false, true>;
+    case 2: return vf::k_env_step<KIND, VF_ACT_BODYRATE, VF_INT_RK4, false, false, true>;
+    default: return vf::k_env_step<KIND, VF_ACT_BODYRATE, VF_INT_RK4, true, false, true>;
+    }
+}
+
+// g: the launch's arguments as launch_env_step filled them in.  Every condition k_env_step<STRAIGHT> builds on is tested here; any
+// other configuration keeps the general kernel
+EnvStepKernel pick_env_kernel(const vf_env* h, const vf::EnvArgs& g)
 {
     const bool lazy = h->dyn.Npad > 2 * 65536;          // more than two waves per SIMD (k_env_step, LAZY_SLOT)
+    const bool straight = !lazy && g.d.g_drag < 0 && !g.d.wind && !g.out.done_list && !g.out.done_count && !g.stale && g.auto_reset &&
+                          g.g_spawn_rd >= 0 && g.helper > 0 && h->cfg.obs_mode == VF_OBS_STATE && h->dyn.cfg.action_type == VF_ACT_BODYRATE;
+    if (straight && h->cfg.kind == VF_ENV_HOVER) return pick_env_straight_k<VF_ENV_HOVER>(h->dyn.cfg);
+    if (straight && h->cfg.kind == VF_ENV_NAV) return pick_env_straight_k<VF_ENV_NAV>(h->dyn.cfg);
     switch (h->cfg.kind) {
     case VF_ENV_HOVER: return pick_env_kernel_k<VF_ENV_HOVER>(h->dyn.cfg, lazy);
     case VF_ENV_NAV: return pick_env_kernel_k<VF_ENV_NAV>(h->dyn.cfg, lazy);
@@ -501,7 +547,7 @@ int launch_env_step(vf_env* h, const float* action, const vf_env_out* out, int a
         } else {
             h->stale_all = 1;
         }
-        hipLaunchKernelGGL(pick_env_kernel(h), dim3(nb), dim3(vf::kBlock), 0, st, h->dyn.d_cfg, h->d_cfg, g.d.S, g.d.action, g.d.N, g.d.G,
+        hipLaunchKernelGGL(pick_env_kernel(h, g), dim3(nb), dim3(vf::kBlock), 0, st, h->dyn.d_cfg, h->d_cfg, g.d.S, g.d.action, g.d.N, g.d.G,
                            g.d.head, g.helper, h->dyn.cfg.delay_steps, g.d.g_drag, g);
     }
     VF_HIP(hipGetLastError());
@@ -527,7 +573,7 @@ int vf_env_create(const vf_dyn_cfg* dyn, const vf_env_cfg* env, int32_t N, int32
     h->cfg = *env;
     h->g_race = racing ? h->dyn.g_extra : -1;
     h->g_spawn = env->spawn_prefetch ? h->dyn.g_extra + racing : -1;
-    int rc = vf::upload_cfg(h->dyn.cfg, &h->dyn.d_cfg);
+    int rc = vf::upload_dyn_dev(h->dyn.cfg, &h->dyn.d_cfg);
     if (rc == VF_OK) rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg);
     if (rc == VF_OK && h->g_spawn >= 0 &&
         hipMalloc(reinterpret_cast<void**>(&h->d_stale), (size_t)2 * (h->dyn.Npad / 64) * sizeof(unsigned long long)) != hipSuccess) {

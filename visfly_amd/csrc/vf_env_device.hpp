@@ -31,6 +31,10 @@ struct Collision {
 };
 
 // DroneEnvsBase.update_collision, bbox branch (envs/base/droneEnv.py:345-369)
+// NO_ROOT: for a caller that reads only `hit` and `oob` (the hover kinds' step): the test sqrtf(y) < uav_radius is taken as y < hit_y,
+// the same predicate for every y (hit_threshold, vf_step_consts.hpp), and `dis` is left at y, the SQUARED distance.  `e` must be the
+// handle's device block (env_hit_y)
+template <bool NO_ROOT = false>
 __device__ __forceinline__ Collision bbox_collision(const vf_env_cfg& e, const float* p)
 {
     Collision c;
@@ -50,16 +54,37 @@ __device__ __forceinline__ Collision bbox_collision(const vf_env_cfg& e, const f
         c.oob = c.oob || (p[d] < e.bbox_lo[d]) || (p[d] > e.bbox_hi[d]);
         c.vec[d] = c.cp[d] - p[d];
     }
-    c.dis = norm3(c.vec[0], c.vec[1], c.vec[2]);
-    c.hit = c.dis < e.uav_radius;
+    if constexpr (NO_ROOT) {
+        c.dis = __builtin_fmaf(c.vec[2], c.vec[2], __builtin_fmaf(c.vec[1], c.vec[1], c.vec[0] * c.vec[0]));
+        c.hit = c.dis < env_hit_y(e);
+    } else {
+        c.dis = norm3(c.vec[0], c.vec[1], c.vec[2]);
+        c.hit = c.dis < e.uav_radius;
+    }
     return c;
 }
 
 // HoverEnv.get_reward (envs/HoverEnv.py:83-94), also the positional RacingEnv reward
+// PAIRED: the four norms' square roots as one sqrt_p2 (vf_pair_algebra.hpp), the same operations
+template <bool PAIRED = false>
 __device__ __forceinline__ float hover_reward(const float* p, const float* tgt, const Quat& q, const float* v,
                                               const float* w)
 {
     const float c1 = (float)(-0.1 * 1 / 9), c2 = (float)-0.00001, c3 = (float)-0.002;
+    if constexpr (PAIRED) {
+        const float dx = p[0] - tgt[0], dy = p[1] - tgt[1], dz = p[2] - tgt[2], qw = q.w - 1.0f;
+        const float y0 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+        const float y1 = __builtin_fmaf(q.z, q.z, __builtin_fmaf(q.y, q.y, __builtin_fmaf(q.x, q.x, qw * qw)));
+        const float y2 = __builtin_fmaf(v[2], v[2], __builtin_fmaf(v[1], v[1], v[0] * v[0]));
+        const float y3 = __builtin_fmaf(w[2], w[2], __builtin_fmaf(w[1], w[1], w[0] * w[0]));
+        vf_f2 n01, n23;
+        sqrt_p2(pair_of(y0, y1), pair_of(y2, y3), n01, n23);
+        float r = 0.1f + n01[0] * c1;
+        r = r + n01[1] * c2;
+        r = r + n23[0] * c3;
+        r = r + n23[1] * c3;
+        return r;
+    }
     float r = 0.1f + norm3(p[0] - tgt[0], p[1] - tgt[1], p[2] - tgt[2]) * c1;
     r = r + norm4(q.w - 1.0f, q.x, q.y, q.z) * c2;
     r = r + norm3(v[0], v[1], v[2]) * c3;

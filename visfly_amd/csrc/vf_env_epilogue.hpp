@@ -118,7 +118,9 @@ __device__ __forceinline__ SpawnSlot load_spawn_slot(const EnvArgs& g, int i, bo
 // row hand-over at the end depends on the lane <-> agent map
 // (storing what the interval finalises BEFORE collision / reward / counters, with write-through or non-temporal policies, was measured:
 // 0.3 us off the headline regime only, profiles/r04_env_quad.txt; not kept)
-template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false>
+// STRAIGHT (k_env_step<STRAIGHT>, vf_env.hip): the rows are known on the host to be the raw state rows, obs_mode is not read; the hover
+// reward's square roots are taken as pairs and the hover kind's collision test without its root -- the same results, bit for bit
+template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false, int STRAIGHT = 0>
 __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_cfg& e, const EnvArgs& g, int i, bool live,
                                              Agent& s, Spares& sp, int wave_first, float* tile, float* reward_reg = nullptr,
                                              bool* done_reg = nullptr, unsigned long long* tr = nullptr)   // tr: -DVF_ENV_TRACE builds only
@@ -130,7 +132,9 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
 #endif
     EnvRegs er = unpack_env(sp);
     const float vel[3] = {s.v[0] + s.wnd[0], s.v[1] + s.wnd[1], s.v[2] + s.wnd[2]};  // dynamics.py:751-752
-    Collision col = bbox_collision(e, s.p);
+    // (the hover kind reads nothing of the collision but its flags, the navigation reward reads the distance)
+    constexpr bool NO_ROOT = (STRAIGHT & 4) && KIND == VF_ENV_HOVER && !EXT;
+    Collision col = bbox_collision<NO_ROOT>(e, s.p);
     if constexpr (EXT) {   // visual branch of update_collision (droneEnv.py:330-342,364-367): the scene manager's closest point
         if (g.ext_point && live) {
             const float* q = g.ext_point + 3 * (size_t)i;
@@ -174,7 +178,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
                                               // refreshed before get_success() advances it (droneGymEnv.py:161-166,197-208)
     float4 race = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (KIND == VF_ENV_HOVER) {
-        reward = hover_reward(s.p, e.target, s.q, vel, s.w);
+        reward = hover_reward<(STRAIGHT & 2) != 0>(s.p, e.target, s.q, vel, s.w);
     } else if constexpr (KIND == VF_ENV_NAV) {
         if (e.reward_mode == VF_REWARD_NAV2) {
             reward = nav2_reward(e, s.p, vel, s.w, success);
@@ -215,7 +219,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
     }
     float o[13];
     obs_row(c, s, o);
-    obs_variant(e, o);
+    if constexpr (!(STRAIGHT & 1)) obs_variant(e, o);
     if (live) {
         g.out.reward[i] = reward;
         if (reward_reg) *reward_reg = reward;       // (callers that keep going with the agent in registers: vf_bptt_rollout.hip)
@@ -281,14 +285,14 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
             *granule(g.d.S, g.d.G, i, g.d.g_drag) = kl4;
             *granule(g.d.S, g.d.G, i, g.d.g_drag + 1) = kq4;
         }
-        col = bbox_collision(e, s.p);                                                       // droneEnv.py:285-288
+        col = bbox_collision<NO_ROOT>(e, s.p);                                              // droneEnv.py:285-288
         er.flags = (int)(episode << 8);
         er.flags = set_flag(er.flags, VF_F_COLLISION, col.hit);
         er.flags = set_flag(er.flags, VF_F_OUT_BOUNDS, col.oob);
         er.step_count = 0;                                                                  // :387-392
         er.rewards = 0.0f;
         obs_row(c, s, o);
-        obs_variant(e, o);
+        if constexpr (!(STRAIGHT & 1)) obs_variant(e, o);
     }
     if constexpr (kind_is_racing(KIND)) {
         race.x = __int_as_float(gate);

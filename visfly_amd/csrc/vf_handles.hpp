@@ -1,6 +1,7 @@
 // Host-side handle layouts shared by the translation units of libvisfly_amd.so.
 #pragma once
 #include "vf_common.hpp"
+#include "vf_step_consts.hpp"
 
 struct vf_dyn {
     vf_dyn_cfg cfg;
@@ -82,10 +83,21 @@ inline int upload_cfg(const T& host, T** dev)
     VF_HIP(hipMemcpy(*dev, &host, sizeof(T), hipMemcpyHostToDevice));
     return VF_OK;
 }
+// a dynamics handle's block: cfg + the packed step constants behind it (vf_step_consts.hpp); freed by release_cfg.  The only place
+// that writes the device copy of a vf_dyn_cfg the step kernels read: whoever rewrites it later goes through here again
+inline int upload_dyn_dev(const vf_dyn_cfg& cfg, vf_dyn_cfg** dev)
+{
+    vf_dyn_dev host{};
+    host.cfg = cfg;
+    pack_step_consts(cfg, &host.k);
+    if (!*dev) VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(vf_dyn_dev)));
+    VF_HIP(hipMemcpy(*dev, &host, sizeof(vf_dyn_dev), hipMemcpyHostToDevice));
+    return VF_OK;
+}
 // an env handle's block: cfg + agent0 (allocated on first use, rewritten in place afterwards: the kernels keep the address)
 inline int upload_env_dev(const vf_env_cfg& cfg, unsigned agent0, vf_env_cfg** dev)
 {
-    const vf_env_dev host{cfg, agent0, 0u};
+    const vf_env_dev host{cfg, agent0, hit_threshold(cfg.uav_radius)};
     if (!*dev) VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(vf_env_dev)));
     VF_HIP(hipMemcpy(*dev, &host, sizeof(vf_env_dev), hipMemcpyHostToDevice));
     return VF_OK;

@@ -418,4 +418,63 @@ VF_PA_FN void div_p1(const vf_f2 a, const float ax, const float b, vf_f2& o, flo
 #endif
 }
 
+// ---- IEEE square root of two pairs ---------------------------------------------------------------------------------------------------
+// hipcc expands sqrtf in the backend into one dependent chain per root (read off its code for the roots outside the sub-step loop):
+//   s = x < 2^-96;  a = s ? x * 2^32 : x;  r = v_sqrt(a);  d = float(int(r) - 1);  e = fma(-d, r, a);  r1 = 0 >= e ? d : r;
+//   u = float(int(r) + 1);  f = fma(-u, r, a);  r2 = 0 < f ? u : r1;  r3 = s ? r2 * 2^-16 : r2;  result = class(a, +-0 | +inf) ? a : r3
+// with two or three s_nop pads behind its compares.  sqrt_p2 restates that sequence for FOUR roots, every operation and operand kept: the
+// two multiplies and the two residual FMAs of each pair are v_pk_mul_f32 / v_pk_fma_f32 (the negation on neg_lo / neg_hi), v_sqrt, the
+// integer steps, the compares and the selects stay per root.  The two pairs' steps alternate behind scheduling barriers as in div_p2, so
+// that no packed instruction reads the one before it and the compares of four roots stand between a compare and its select.  The same
+// correctly rounded root for every input, no guard, no range assumption (tools/sqrt_pair_probe.hip compares it with sqrtf bit for bit).
+// the float k integer steps from r (by value: __builtin_bit_cast of a vector ELEMENT reads element 0 with this compiler)
+VF_PA_FN float ulp_step(float r, int k) { return __builtin_bit_cast(float, __builtin_bit_cast(int, r) + k); }
+VF_PA_FN void sqrt_p2(const vf_f2 xa, const vf_f2 xb, vf_f2& oa, vf_f2& ob)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VF_PA_SEL2(c, t, f) {c##0 ? t[0] : f[0], c##1 ? t[1] : f[1]}
+#define VF_PA_STEP2(r, k) {ulp_step(r[0], k), ulp_step(r[1], k)}
+    const vf_f2 up = {0x1p+32f, 0x1p+32f}, down = {0x1p-16f, 0x1p-16f};
+    const bool sa0 = xa[0] < 0x1p-96f, sa1 = xa[1] < 0x1p-96f, sb0 = xb[0] < 0x1p-96f, sb1 = xb[1] < 0x1p-96f;
+    const vf_f2 ua = xa * up;
+    VF_PA_SB;
+    const vf_f2 ub = xb * up;
+    VF_PA_SB;
+    const vf_f2 a = VF_PA_SEL2(sa, ua, xa), b = VF_PA_SEL2(sb, ub, xb);
+    const vf_f2 ra = {__builtin_amdgcn_sqrtf(a[0]), __builtin_amdgcn_sqrtf(a[1])}, rb = {__builtin_amdgcn_sqrtf(b[0]), __builtin_amdgcn_sqrtf(b[1])};
+    const vf_f2 da = VF_PA_STEP2(ra, -1), db = VF_PA_STEP2(rb, -1);
+    VF_PA_SB;
+    const vf_f2 ea = __builtin_elementwise_fma(-da, ra, a);
+    VF_PA_SB;
+    const vf_f2 eb = __builtin_elementwise_fma(-db, rb, b);
+    VF_PA_SB;
+    const bool ca0 = 0.0f >= ea[0], ca1 = 0.0f >= ea[1], cb0 = 0.0f >= eb[0], cb1 = 0.0f >= eb[1];
+    vf_f2 va = VF_PA_SEL2(ca, da, ra), vb = VF_PA_SEL2(cb, db, rb);
+    const vf_f2 pa = VF_PA_STEP2(ra, 1), pb = VF_PA_STEP2(rb, 1);
+    VF_PA_SB;
+    const vf_f2 fa = __builtin_elementwise_fma(-pa, ra, a);
+    VF_PA_SB;
+    const vf_f2 fb = __builtin_elementwise_fma(-pb, rb, b);
+    VF_PA_SB;
+    const bool ga0 = 0.0f < fa[0], ga1 = 0.0f < fa[1], gb0 = 0.0f < fb[0], gb1 = 0.0f < fb[1];
+    const vf_f2 wa = VF_PA_SEL2(ga, pa, va), wb = VF_PA_SEL2(gb, pb, vb);
+    VF_PA_SB;
+    const vf_f2 ta = wa * down;
+    VF_PA_SB;
+    const vf_f2 tb = wb * down;
+    VF_PA_SB;
+    va = VF_PA_SEL2(sa, ta, wa);
+    vb = VF_PA_SEL2(sb, tb, wb);
+    const bool za0 = __builtin_amdgcn_classf(a[0], 0x260), za1 = __builtin_amdgcn_classf(a[1], 0x260);
+    const bool zb0 = __builtin_amdgcn_classf(b[0], 0x260), zb1 = __builtin_amdgcn_classf(b[1], 0x260);
+    oa = VF_PA_SEL2(za, a, va);
+    ob = VF_PA_SEL2(zb, b, vb);
+#undef VF_PA_SEL2
+#undef VF_PA_STEP2
+#else
+    oa = pair_of(__builtin_sqrtf(xa[0]), __builtin_sqrtf(xa[1]));
+    ob = pair_of(__builtin_sqrtf(xb[0]), __builtin_sqrtf(xb[1]));
+#endif
+}
+
 }  // namespace vf
