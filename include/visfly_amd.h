@@ -697,8 +697,10 @@ int vf_gather_rows(const vf_gather_fields* fields, const int64_t* perm, int64_t 
 
 /* Post-step bookkeeping of the rollout loop (SB3 OnPolicyAlgorithm.collect_rollouts; utils/algorithms/PPO.py:146): the
  * TimeLimit bootstrap reward_out = reward + gamma * V(terminal_observation) where the episode ended by truncation
- * (done && ep_flags bit 1, vf_env_out.ep_flags), and the next step's episode_start flags = float(done).  One launch instead
- * of a chain of elementwise tensor ops. */
+ * (done && ep_flags bit 1, vf_env_out.ep_flags), and the next step's episode_start flags = float(done).  Rows that did not
+ * truncate are copied, not recomputed: reward_out keeps their bits (-0.0 stays -0.0) and their terminal_value is never read into
+ * the result, so it may be non-finite there -- as in SB3 (`rewards[idx] += gamma * terminal_value` on the truncated idx only) and
+ * in the deferred path below.  One launch instead of a chain of elementwise tensor ops. */
 int vf_rollout_post(const float* reward, const uint8_t* done, const uint8_t* ep_flags, const float* terminal_value, float gamma,
                     float* reward_out, float* next_episode_start, int32_t N, vf_stream_t stream);
 

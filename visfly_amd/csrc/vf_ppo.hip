@@ -187,8 +187,10 @@ __global__ __launch_bounds__(kBlock) void k_rollout_post(const float* __restrict
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= N) return;
     const bool d = done[i] != 0;
-    const float trunc = (d && (ep_flags[i] & 2)) ? 1.0f : 0.0f;
-    reward_out[i] = reward[i] + (gamma * tv[i]) * trunc;
+    // a select, not a multiply by 0 / 1: SB3 adds to the truncated rows only, so every other reward keeps its bits (-0.0 stays -0.0,
+    // a non-finite terminal value of a row that did not truncate never reaches its reward), as in k_rollout_post_collect + scatter
+    const float r = reward[i];
+    reward_out[i] = (d && (ep_flags[i] & VF_EP_TRUNCATED)) ? r + gamma * tv[i] : r;
     next_start[i] = d ? 1.0f : 0.0f;
 }
 
