@@ -865,7 +865,9 @@ int vf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  *   desc          the policy's layer table with the `save` pointers of slot 0; the slots of the horizon are stored back to back
  *                 ([H][N][w] per buffer), so row t N + i addresses slot t (as for vf_mlp_weight_grad over a horizon)
  *   obs_slots0/1  [H][N][w] observation copies of the slots; slot 0 holds the current observation, slot t + 1 is written by
- *                 step t (obs_slots1 = the constant "target" rows of NavigationEnv, filled by the caller, or NULL)
+ *                 step t (obs_slots1 = the constant "target" rows of NavigationEnv, filled by the caller, or NULL; over a racing env
+ *                 and a two-input layer table whose second input is 1 wide: the "gate" index as a float column -- slot 0 filled by
+ *                 the caller, slot t + 1 WRITTEN by step t from the index the launch holds: hence not `const`)
  *   eps, actions  [H][N][4]: reparameterisation noise in, actions out (the tape's action rows)
  *   out           episode outputs as for vf_env_step; out->reward = N floats of scratch; obs / done are ignored
  *   obs_final     (N,13) observation after the last step;  tape [H] rows of tape_stride floats;  tape_done [H][N]
@@ -896,7 +898,7 @@ int vf_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  *   reward_rows   [H][N] the reward of every step;  ep_flag_rows [H][N] bytes = out->ep_flags of the step, written where done
  *                 (needs out->ep_flags; shac.py:231-232 reads `episode_done` only there) */
 int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* params, const float* packed, const float* obs_slots0,
-                    const float* obs_slots1, const float* log_std, const float* eps, float* actions, const vf_env_out* out,
+                    float* obs_slots1, const float* log_std, const float* eps, float* actions, const vf_env_out* out,
                     float* obs_final, float* tape, int64_t tape_stride, uint8_t* tape_done, float* d_reward, float* loss,
                     float* disc, float gamma, float scale, int32_t H, float* substep_tape, float* mean_rows, float* log_std_rows,
                     float* reward_rows, uint8_t* ep_flag_rows, vf_stream_t stream);
@@ -933,8 +935,10 @@ int vf_bptt_reverse(vf_env* h, const vf_mlp_bwd_desc* desc, const float* packed,
 typedef struct vf_ppo_rollout_args {
     int32_t T, w1, capacity, pad0;
     float* obs_state;           /* [T][N][13] RolloutBuffer "state" rows; row 0 = the current observation (caller), row t + 1 by step t */
-    const float* obs_target;    /* [T][N][w1] "target" rows filled by the caller (NavigationEnv: constant), or NULL */
-    const float* obs_target_row;/* (N,w1) the same for the bootstrap list, or NULL */
+    float* obs_target;          /* [T][N][w1] "target" rows filled by the caller (NavigationEnv: constant), or NULL.  Over a racing env with
+                                   w1 = 1: RolloutBuffer "gate" rows (the index as a float) -- row 0 the caller's, row t + 1 WRITTEN by step t
+                                   (hence not `const`); rows1 then takes the index the terminal "state" row was formed with */
+    const float* obs_target_row;/* (N,w1) the same for the bootstrap list, or NULL (racing + w1 = 1: not read, may be NULL) */
     float* obs_final;           /* (N,13) the observation after the last step */
     float* means;               /* [T][N][4] the head means (what the per-step vf_mlp_forward leaves), or NULL */
     float* values;              /* [T][N] */

@@ -8,7 +8,8 @@ into ``csrc/jit/libvf_chain_<hash>.so`` (four parts in parallel, ~40 s once; cac
 flags) and registers it with the library (vf_chain_plugin_load).  ``__graft_entry__.build()`` pre-builds the shapes the tests use, so
 the GPU box finds them in the snapshot.
 
-Shapes that qualify: 1-2 observation branches of <= 32 columns, 1-4 layers per branch / trunk, widths in multiples of 32 up to 128,
+Shapes that qualify: 1-2 observation branches of <= 32 columns (the second one: NavigationEnv's constant "target" rows, or the racing envs'
+1-wide "gate" column, which the persistent launches of a racing kind take from the index the wave holds instead of from memory), 1-4 layers per branch / trunk, widths in multiples of 32 up to 128,
 the actor-critic heads (4, 1), the SAC-style Actor's (4, 4), or the twin critic's (1, 1) with its pass-through action input behind ONE
 observation branch.  Everything else keeps running on the block-tile kernels (MlpPolicy warns once).
 ``VISFLY_AMD_JIT=0`` switches the compilation off.
@@ -48,6 +49,9 @@ PREBUILD = {
     "ragged": ({"state": 13, "target": 3}, {"state": [96, 64, 32], "target": [32]}, [32, 32, 32], [128]),
     # 30 forward tiles: the fused PPO step keeps the ReLU masks as bits (csrc/vf_mlp_chain_gen.hpp: kGenLiveTiles)
     "wide": ({"state": 13, "target": 3}, {"state": [128, 64], "target": [128, 64]}, [128, 128], [128, 128]),
+    # StateGateExtractor on the racing envs (tests/test_gate_extractor_gpu.py): the second branch is the 1-wide gate column (KIN 8).
+    # RacingEnv2's 16 and RacingEnv's 13 state columns both pad to KIN 16: one class
+    "gate_pi": ({"state": 16, "gate": 1}, {"state": [64, 32], "gate": [32]}, [32], [32]),
 }
 # the SAC-style Actor (heads (4, 4); td_policies.Actor: `pi` = latent_pi, `vf` = log_latent_pi) on a non-default shape: (.., head_dims)
 # the reference policy's DEFAULT activations (Tanh trunks, policies.py:108; ReLU extractor MLPs, extractors.py:666) on the YAMLs' shapes:
@@ -77,6 +81,7 @@ PREBUILD_SAC = {
     "sac_nav": ({"state": 13, "target": 3}, {"state": [128, 64], "target": [64]}, [128, 64], [64], (4, 4)),
     "sac_hover": ({"state": 13}, {"state": [64, 64, 32]}, [32], [32], (4, 4)),      # (the Actor BPTT builds for pi=[32]: log_latent_pi mirrors latent_pi)
     "sac_nav_bptt": ({"state": 13, "target": 3}, {"state": [64, 64], "target": [32]}, [64], [64], (4, 4)),      # ... over StateTargetExtractor, pi=[64]
+    "gate_sac": ({"state": 16, "gate": 1}, {"state": [64, 32], "gate": [32]}, [32], [32], (4, 4)),              # ... over StateGateExtractor (BPTT's Actor, SHAC)
 }
 # ... and their roll-out plugins for the configurations tests/test_ppo_gpu.py runs: (shape name, (VF_ENV_*, VF_ACT_*, VF_INT_*, ctrl_delay))
 # ... and the BPTT plugins (both persistent launches of a horizon) tests/test_chain_jit_gpu.py runs: (shape name in PREBUILD_SAC / PREBUILD,
@@ -85,9 +90,12 @@ PREBUILD_BPTT = [("sac_hover", (0, 1, 0, True)), ("sac_nav_bptt", (1, 1, 0, True
                  ("sac_hover", (3, 0, 0, True)),        # RacingEnv2: kernel-side kind VF_ENV_RACING2, thrust
                  ("sac_hover_tanh", (0, 1, 0, True)), ("sac_hover_elu", (0, 1, 0, True)), ("sac_hover_leaky", (0, 1, 0, True)),
                  ("pi_hover_tanh", (0, 1, 0, True)), ("pi_hover_elu", (0, 1, 0, True)), ("pi_hover_leaky", (0, 1, 0, True)),
-                 ("sac_hover_tanh", (2, 0, 0, True))]   # RacingEnv, thrust
+                 ("sac_hover_tanh", (2, 0, 0, True)),   # RacingEnv, thrust
+                 # StateGateExtractor: the gate column as branch 1 over the racing kinds (RacingEnv2 / RacingEnv, thrust)
+                 ("gate_sac", (3, 0, 0, True)), ("gate_pi", (3, 0, 0, True)), ("gate_sac", (2, 0, 0, True))]
 PREBUILD_ROLLOUT = [("verdict", (1, 1, 0, True)), ("one_layer_extractor", (0, 1, 1, False)), ("one_layer_extractor", (1, 1, 0, True)),
-                    ("one_layer_extractor", (2, 1, 0, True)), ("one_layer_extractor", (3, 1, 0, True))]      # RacingEnv / RacingEnv2 (kernel-side kind 3)
+                    ("one_layer_extractor", (2, 1, 0, True)), ("one_layer_extractor", (3, 1, 0, True)),      # RacingEnv / RacingEnv2 (kernel-side kind 3)
+                    ("gate_pi", (3, 1, 0, True))]                                                             # StateGateExtractor on RacingEnv2
 
 
 def shape_of(obs_dims, extractor, pi, vf, head_dims=(4, 1), passthrough=(), acts=(1, 1)):

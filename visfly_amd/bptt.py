@@ -9,6 +9,11 @@ Where the reference relies on a torch autograd tape of ~3.8k nodes per control s
 simulator's reverse pass is the hand-written adjoint kernel ``vf_env_step_bwd`` (one launch per
 step) and the policy's is the MFMA linear-layer kernels; ``torch.autograd`` is only the scheduler
 that orders those launches (two custom Functions), so any torch policy can be dropped in as well.
+
+Extractors: ``StateExtractor``, ``StateTargetExtractor`` and, on the racing envs, ``StateGateExtractor`` (both actors): the "gate" index
+is fed as one float32 column holding the agent's current gate, carries no gradient (``env.backward_step`` receives d obs["state"] only),
+and on the persistent launches of a generated class comes from the index the wave holds.  Not part of this: a full ``BPTT.learn``
+fixture of the reference on the racing envs (the loop is pinned by bptt_loop_hover*, RacingEnv2's adjoint by bptt_racing2_thrust).
 """
 import ctypes as C
 import os
@@ -18,7 +23,7 @@ from typing import Dict, Optional
 import torch as th
 
 from . import _lib, checkpoint, parallel
-from .ppo import MlpPolicy, _ptr
+from .ppo import INDEX_OBS_KEYS, MlpPolicy, _ptr, obs_width, policy_rows, trainer_obs_keys
 
 
 class EnvStepFunction(th.autograd.Function):
@@ -87,9 +92,10 @@ class BPTT:
         if not env._is_initial:
             env.reset()
         obs = env.get_observation()
-        self.obs_keys = [k for k in obs.keys() if k in ("state", "target")]
-        if hasattr(env, "obs_gate_exact"):       # RacingEnv: the policy does not read "gate"; skip its per-step bookkeeping launches
-            env.obs_gate_exact = False
+        self.obs_keys = trainer_obs_keys(obs, policy_kwargs)
+        if hasattr(env, "obs_gate_exact"):       # RacingEnv: skip the per-step bookkeeping launches of the returned "gate" entry; a policy
+            env.obs_gate_exact = False           # that reads it (StateGateExtractor) is fed the agent's CURRENT gate, the index its "state"
+                                                 # rows are formed with
         self.policy = self._make_policy(obs, policy_kwargs, seed)
         self.policy.lazy_pack = True        # this trainer calls mark_updated() after every optimiser step
         self.world, self.rank = parallel.world_size(), parallel.rank()
@@ -150,7 +156,7 @@ class BPTT:
         arch = list(pk.get("pi", [64, 64]))
         if self._critic_arch is None:
             self._critic_arch = list(arch)
-        pol = MlpPolicy({k: obs[k].shape[1] for k in self.obs_keys}, self._extractor, arch, arch, self.device, seed=seed,
+        pol = MlpPolicy({k: obs_width(obs[k]) for k in self.obs_keys}, self._extractor, arch, arch, self.device, seed=seed,
                         ortho_init=False, head_dims=(4, 4), log_std_param=False, activation=act, extractor_activation=ext_act)
         hidden = lambda trunk: [ly for ly in pol.layers if ly.dst.startswith(trunk + ":")]
         for a, b in zip(hidden("pi"), hidden("vf")):                  # log_latent_pi starts as a copy of latent_pi
@@ -198,7 +204,7 @@ class BPTT:
         pk = checkpoint.policy_kwargs_from_reference(pk, self.obs_keys)
         act, ext_act = self._activations(pk)
         self.weight_decay = pk.get("weight_decay", self.weight_decay)
-        return MlpPolicy({k: obs[k].shape[1] for k in self.obs_keys},
+        return MlpPolicy({k: obs_width(obs[k]) for k in self.obs_keys},
                          pk.get("extractor", {k: [128, 64] for k in self.obs_keys}), pk.get("pi", [64, 64]),
                          pk.get("vf", [64, 64]), self.device, log_std_init=pk.get("log_std_init", -1.0), seed=seed,
                          ortho_init=pk.get("ortho_init", True), activation=act, extractor_activation=ext_act)
@@ -240,7 +246,7 @@ class BPTT:
             self._last_rollout = dict(action=acts, reward=th.empty((H, N), **f), done=th.empty((H, N), dtype=th.bool, device=dev))
             obs = env.get_observation()
         for t in range(0 if not fused else H, H):
-            o = {k: obs[k].detach().contiguous() for k in keys}
+            o = policy_rows(obs, keys)
             mu, ls = pol.forward(o, slot=t)                                            # actor.action_log_prob(obs) :113
             self._head_fwd(mu, ls, eps[t], acts[t])                                    # tanh output: the clip of :114-116 is the identity
             obs, reward, done, _ = env._step_no_grad(acts[t], False, record=True, borrow=True)      # :119
@@ -300,7 +306,7 @@ class BPTT:
             fused = env.rollout_policy(pol, self.obs_keys, epss, acts, drews, loss_vec, disc, float(self.gamma), 1.0 / (N * self.world))
         for t in range(0 if not fused else H, H):
             action = acts[t]
-            o = {k: obs[k].detach().contiguous() for k in self.obs_keys}
+            o = policy_rows(obs, self.obs_keys)
             if not (defer and pol.forward_act(o, epss[t], action, slot=t)):      # action head fused into the forward launch
                 mean, _ = pol.forward(o, slot=t, need_value=False)
                 _lib.check(L.vf_reparam_fwd(_ptr(mean), _ptr(log_std), _ptr(epss[t]), _ptr(action), N, st))
@@ -352,7 +358,8 @@ class BPTT:
         obs = env.get_observation()
         epss = self._noise(self.H, N)     # same draw as the reverse sweep
         for t in range(self.H):
-            mean = PolicyFunction.apply(pol, self.obs_keys, anchor, *[obs[k] for k in self.obs_keys])
+            gate = policy_rows(obs, [k for k in self.obs_keys if k in INDEX_OBS_KEYS])      # (the index column: no graph; "state" keeps its own)
+            mean = PolicyFunction.apply(pol, self.obs_keys, anchor, *[gate.get(k, obs[k]) for k in self.obs_keys])
             action = th.tanh(mean + log_std.exp() * epss[t])     # reparameterised squashed Gaussian (td_policies Actor)
             obs, reward, done, _ = env.step(action)
             loss_vec = loss_vec + -1 * reward * disc          # :123
@@ -382,15 +389,14 @@ class BPTT:
         """SB3-style predict (utils/evaluate.py:94): -> (action, None); deterministic: a = tanh(mean)"""
         N = obs[self.obs_keys[0]].shape[0]
         if self.reference_actor:         # shac.py:334-343 / MTDPolicy.predict
-            mu, ls = self.policy.forward({k: obs[k].detach().contiguous() for k in self.obs_keys}, save_activations=False, slot=self.H + 1)
+            mu, ls = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1)
             if deterministic:
                 return th.tanh(mu), None
             eps = self._noise(1, N)[0]
             action = th.empty((N, 4), device=self.device)
             self._head_fwd(mu, ls.contiguous(), eps, action)
             return action, None
-        mean, _ = self.policy.forward({k: obs[k].detach().contiguous() for k in self.obs_keys}, save_activations=False,
-                                      slot=self.H + 1, need_value=False)
+        mean, _ = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1, need_value=False)
         if deterministic:
             return th.tanh(mean), None
         eps = self._noise(1, N)[0]
@@ -434,7 +440,8 @@ class BPTT:
     @staticmethod
     def _policy_kwargs_from_spec(spec):
         """the stored network shapes as SB3-style policy_kwargs (what _make_reference_actor parses)"""
-        return dict(features_extractor_class="StateTargetExtractor" if len(spec["extractor"]) > 1 else "StateExtractor",
+        return dict(features_extractor_class="StateGateExtractor" if "gate" in spec["extractor"] else
+                    "StateTargetExtractor" if len(spec["extractor"]) > 1 else "StateExtractor",
                     features_extractor_kwargs={"net_arch": {k: {"layer": list(v)} for k, v in spec["extractor"].items()},
                                                "activation_fn": spec.get("extractor_activation", "relu")},
                     net_arch=dict(pi=list(spec["pi"]), qf=list(spec["qf"])), activation_fn=spec.get("activation", "relu"),

@@ -3,7 +3,8 @@
 * ``load_yaml_config`` / ``policy_kwargs_from_reference``: the ``algorithm:`` / ``env:`` blocks of the reference's
   experiment files (exps/examples/alg_cfgs/*/PPO.yaml, env_cfgs/*.yaml; utils/common.py:232-237) are accepted as they
   are; the SB3-style ``policy_kwargs`` (features_extractor_class / features_extractor_kwargs.net_arch.<key>.layer /
-  net_arch.pi|vf / activation_fn / optimizer_kwargs) are translated to ``MlpPolicy``'s arguments.  Anything the MFMA
+  net_arch.pi|vf / activation_fn / optimizer_kwargs) are translated to ``MlpPolicy``'s arguments; the vector extractors are
+  ``StateExtractor``, ``StateTargetExtractor`` and ``StateGateExtractor`` (the racing envs' "gate" index as a second branch).  Anything the MFMA
   policy does not implement (image extractors, batch norm, recurrent extractors) raises instead of being dropped;
   layer norm (``ln`` / ``pi_ln`` / ``vf_ln``) becomes ``MlpPolicy``'s ``layer_norm``.
 * ``policy_state_dict`` / ``load_policy_state_dict``: the flat parameter buffer <-> the parameter names the
@@ -25,7 +26,7 @@ from typing import Dict, List, Optional
 
 import torch as th
 
-_EXTRACTORS = {"StateExtractor": ("state",), "StateTargetExtractor": ("state", "target")}
+_EXTRACTORS = {"StateExtractor": ("state",), "StateTargetExtractor": ("state", "target"), "StateGateExtractor": ("state", "gate")}
 _HEAD_NAMES = {"mean": "action_net", "value": "value_net"}
 ARCHIVE_VERSION = "2.2.1"       # environment.yml:275 pins stable-baselines3==2.2.1
 
@@ -46,6 +47,17 @@ def load_yaml_config(path: str) -> dict:
     if "env" in cfg:
         cfg["eval_env"] = deep_merge(cfg["env"], cfg.get("eval_env") or {})
     return cfg
+
+
+def extractor_keys(pk: Optional[dict], obs_keys: List[str]) -> tuple:
+    """the observation keys the extractor of `pk` reads (SB3-style or native policy_kwargs), by the rule of
+    ``policy_kwargs_from_reference``: the named class's, else StateTargetExtractor's where the env has a "target", else StateExtractor's.
+    An unknown class name gives () -- the translation raises for it"""
+    pk = pk or {}
+    if "extractor" in pk:
+        return tuple(pk["extractor"].keys())
+    cls = pk.get("features_extractor_class", "StateTargetExtractor" if "target" in obs_keys else "StateExtractor")
+    return _EXTRACTORS.get(cls if isinstance(cls, str) else cls.__name__, ())
 
 
 def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dict:
@@ -147,8 +159,32 @@ def policy_state_dict(policy) -> Dict[str, th.Tensor]:
     return sd
 
 
+def _check_shapes(policy, sd):
+    """every layer's tensors before any is copied: a refused state_dict leaves the policy as it was.  Shapes first (ValueError at the
+    first layer, in schedule order, whose tensors are there with another shape -- a network with or without an extractor branch differs
+    in the trunks' first layers at the latest), then missing names (KeyError)"""
+    missing = None
+    for ly, prefixes in _names(policy):
+        p = next((p for p in prefixes if p + ".weight" in sd), None)
+        if p is None:
+            missing = missing or f"state_dict has none of {[q + '.weight' for q in prefixes]}"
+            continue
+        w, b = sd[p + ".weight"], sd[p + ".bias"]
+        if tuple(w.shape) != (ly.No, ly.K) or tuple(b.shape) != (ly.No,):
+            raise ValueError(f"{p}: shape {tuple(w.shape)} does not match the policy's layer ({ly.No}, {ly.K})")
+        if ly.ln:
+            q = _ln_prefixes(prefixes)[prefixes.index(p)]
+            if q + ".weight" not in sd or q + ".bias" not in sd:
+                missing = missing or f"state_dict has no {q}.weight / .bias (the LayerNorm behind {p})"
+            elif tuple(sd[q + ".weight"].shape) != (ly.No,) or tuple(sd[q + ".bias"].shape) != (ly.No,):
+                raise ValueError(f"{q}: shape {tuple(sd[q + '.weight'].shape)} does not match the policy's LayerNorm ({ly.No},)")
+    if missing:
+        raise KeyError(missing)
+
+
 def load_policy_state_dict(policy, sd: Dict[str, th.Tensor], strict: bool = True):
     used = set()
+    _check_shapes(policy, sd)
     with th.no_grad():
         for ly, prefixes in _names(policy):
             p = next((p for p in prefixes if p + ".weight" in sd), None)

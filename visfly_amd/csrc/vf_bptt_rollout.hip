@@ -26,7 +26,8 @@ namespace vf {
 
 // the class a horizon steps: the SAC-style Actor (both trunks), or the policy-only class of an actor-critic.  A second observation:
 // required by the state + target classes; refused by a one-observation class over the Navigation kind (NavigationEnv2) and over
-// RacingEnv2's rows, ignored over the Hover and Racing kinds
+// RacingEnv2's rows, ignored over the Hover and Racing kinds; a two-observation class over a racing kind reads the gate column
+// (StateGateExtractor: RollArgs::gate_slots), built-in and generated classes alike
 template <class Net, class NetPi>
 int Builtin<Net, NetPi>::bptt_rollout(const vf_mlp_desc* d, const float* params, int env_kind, const vf_dyn_cfg* c, int has_target,
                                       const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc,
@@ -37,6 +38,10 @@ int Builtin<Net, NetPi>::bptt_rollout(const vf_mlp_desc* d, const float* params,
     if (NetR::NB == 2 ? !has_target : has_target && (env_kind == VF_ENV_NAV || env_kind == VF_ENV_RACING2)) return 0;
     const EnvArgs& ge = *static_cast<const EnvArgs*>(env_args);
     const RollArgs& r = *static_cast<const RollArgs*>(roll_args);
+    // a two-observation class over a racing kind reads the gate column (1 wide, slots written by the launch); over the Navigation kind
+    // the constant target rows
+    if (NetR::NB == 2 && (env_kind == VF_ENV_RACING || env_kind == VF_ENV_RACING2) && (!r.gate_slots || d->in_dim[1] != 1)) return 0;
+    if (NetR::NB == 2 && env_kind != VF_ENV_NAV && env_kind != VF_ENV_RACING && env_kind != VF_ENV_RACING2) return 0;
     return c->ctrl_delay ? BpttRolloutSet<NetR, true>::launch(env_kind, *c, d_dyn, d_env, ge, *gc, r, N, st)
                          : BpttRolloutSet<NetR, false>::launch(env_kind, *c, d_dyn, d_env, ge, *gc, r, N, st);
 }
@@ -48,7 +53,7 @@ template BpttRolloutFn Builtin<NetSacNav>::bptt_rollout;
 }  // namespace vf
 
 extern "C" int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* params, const float* packed, const float* obs_slots0,
-                               const float* obs_slots1, const float* log_std, const float* eps, float* actions,
+                               float* obs_slots1, const float* log_std, const float* eps, float* actions,
                                const vf_env_out* out, float* obs_final, float* tape, int64_t tape_stride, uint8_t* tape_done,
                                float* d_reward, float* loss, float* disc, float gamma, float scale, int32_t H, float* substep_tape,
                                float* mean_rows, float* log_std_rows, float* reward_rows, uint8_t* ep_flag_rows, vf_stream_t stream)
@@ -89,7 +94,10 @@ extern "C" int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* 
                      reinterpret_cast<const float4*>(eps), reinterpret_cast<float4*>(actions), {nullptr, nullptr}, VF_SAC_LOG_STD_MIN,
                      VF_SAC_LOG_STD_MAX};
     vf::RollArgs r{H, N, tape, tape_stride, tape_done, d_reward, loss, disc, const_cast<float*>(obs_slots0), obs_final, gamma, scale, reinterpret_cast<float4*>(substep_tape), reward_rows,
-                   ep_flag_rows};
+                   ep_flag_rows,
+                   // a racing env's second observation is the gate column (StateGateExtractor): obs_slots1 = the slots' "obs:gate", [H][N][1],
+                   // slot 0 the caller's, the later slots written by the launch
+                   h->cfg.kind == VF_ENV_RACING && desc->n_inputs == 2 && desc->in_dim[1] == 1 ? obs_slots1 : nullptr};
     const int rc = vf::chain_serve("vf_bptt_rollout", true, &vf::ChainPlugin::bptt_rollout, desc, params, race2 ? vf::VF_ENV_RACING2 : h->cfg.kind,
                                    &h->dyn.cfg, obs_slots1 != nullptr, h->dyn.d_cfg, h->d_cfg, &ge, &gc, &r, N, vf::as_stream(stream));
     if (rc < 0) return rc;

@@ -24,6 +24,9 @@ struct RollArgs {
     float4* ck;                // optional sub-step tape [H][S + 3][waves][64] float4 (include/visfly_amd.h, vf_bptt_rollout) or null
     float* reward_rows;        // optional [H][N]: the reward of every step (SHAC's horizon buffer, shac.py:259-266)
     unsigned char* ep_flag_rows;   // optional [H][N]: out->ep_flags of the step, written where done (shac.py:231-232 reads episode_done there)
+    // racing kinds, two-branch class (StateGateExtractor): [H][N] = the slots' "obs:gate" column, the gate index as a float.  Slot 0 is
+    // the caller's, slot t + 1 is written by step t (the weight gradient of the branch's first layer reads the slots).  Else null
+    float* gate_slots;
 };
 
 // control_interval_quad observer (component layout: lane 4 m + k holds component k of agent slot m's quantities): the agent at the
@@ -82,6 +85,8 @@ __global__ __launch_bounds__(64) void k_bptt_rollout(const vf_dyn_cfg* __restric
     const vf_dyn_cfg& c = *cp;
     const vf_env_cfg& e = *ep;
     constexpr int OW = obs_width(KIND);       // 13, or RacingEnv2's 16 gate-relative columns
+    // branch 1 of a two-branch class over a racing kind: the gate column (one float: the index, exact), held by the wave
+    constexpr bool GATE = Net::NB == 2 && kind_is_racing(KIND);
     __shared__ __attribute__((aligned(16))) float tile[64 * 13];
     __shared__ float4 act_lds[16];      // the action rows of the step: chain lanes (m, gq = 0) -> the quad of agent slot m
     const int lane = threadIdx.x, m = lane & 15;
@@ -107,6 +112,10 @@ __global__ __launch_bounds__(64) void k_bptt_rollout(const vf_dyn_cfg* __restric
         for (int k = 0; k < 4; ++k) std_reg[k] = expf(gc.rp_log_std[k]);
     }
     const int Gx = g.d.G;
+    // the gate column of policy row m (chain lanes (m, gq)): slot 0 is the caller's; afterwards the index the env epilogue leaves in the
+    // registers of the quad that holds agent slot m (lanes 4 m .. 4 m + 3), fetched across lanes -- never read back from memory
+    float gate_col = 0.0f;
+    if constexpr (GATE) gate_col = r.gate_slots[i];
     ChainState16<Net> st;
     chain16_prologue<Net, 0>(gc, st, lane);
     for (int t = 0; t < r.H; ++t) {
@@ -137,6 +146,11 @@ __global__ __launch_bounds__(64) void k_bptt_rollout(const vf_dyn_cfg* __restric
                 // slot t: the weight gradients' X); read back from the slot it would be an L2 round trip behind the store
                 const float* xl = tile + (lane_t & 15) * OW;
                 const bool from_lds = b == 0 && t > 0;
+                if (GATE && b == 1) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) st.x[b][j] = 4 * gq + j == 0 ? gate_col : 0.0f;
+                    continue;
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int k = 4 * gq + j;
@@ -199,7 +213,13 @@ __global__ __launch_bounds__(64) void k_bptt_rollout(const vf_dyn_cfg* __restric
         asm volatile("" :: "v"(eps_touch.x), "v"(eps_touch.y), "v"(eps_touch.z), "v"(eps_touch.w));
         float reward = 0.0f;
         bool done = false;
-        env_epilogue<KIND, false, 4>(c, e, g, ic, live, s, sp, wave_first, tile, &reward, &done);
+        int gate_next = 0;
+        env_epilogue<KIND, false, 4>(c, e, g, ic, live, s, sp, wave_first, tile, &reward, &done, nullptr, GATE ? &gate_next : nullptr);
+        if constexpr (GATE) {
+            const float gn = (float)gate_next;
+            if (t + 1 < r.H) r.gate_slots[(size_t)(t + 1) * r.N + ic] = gn;      // (the quad's lanes: the same value to the same address)
+            gate_col = __shfl(gn, 4 * (lane & 15));
+        }
         ck.outcome(done, -disc * r.scale, gate_pre);
         if (r.reward_rows) r.reward_rows[(size_t)t * r.N + ic] = reward;
         if (r.ep_flag_rows && done && g.out.ep_flags) r.ep_flag_rows[(size_t)t * r.N + ic] = g.out.ep_flags[ic];   // (this lane's own store above)
@@ -266,7 +286,7 @@ extern template struct BpttRolloutSet<NetSacNav, false>;
 namespace vf {
 
 // layout stamp of what a BPTT plugin's roll-out is handed (vf_chain_plugin.hpp: ChainPlugin::bptt_roll_abi)
-constexpr unsigned kBpttRollPluginAbi = 0x42520002u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(RollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
+constexpr unsigned kBpttRollPluginAbi = 0x42520003u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(RollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
                                                                 sizeof(vf_env_dev) * 5u + sizeof(ChainArgs) * 3u);
 
 }  // namespace vf
@@ -288,7 +308,9 @@ int plugin_bptt_rollout(const vf_mlp_desc* d, const float* params, int env_kind,
                         const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st)
 {
     if (env_kind != KIND || c->action_type != ACT || c->integrator != INTEG || (c->ctrl_delay != 0) != DELAY) return 0;
-    if ((NetR::NB == 2) != (has_target != 0) || (NetR::NB == 2 && KIND != VF_ENV_NAV)) return 0;
+    // a second observation: the constant "target" rows over the Navigation kind, the gate column over the racing kinds
+    if ((NetR::NB == 2) != (has_target != 0) || (NetR::NB == 2 && KIND != VF_ENV_NAV && !kind_is_racing(KIND))) return 0;
+    if (NetR::NB == 2 && kind_is_racing(KIND) && (!static_cast<const RollArgs*>(roll_args)->gate_slots || d->in_dim[1] != 1)) return 0;
     if (!chain_matches_gen<NetR>(*d) || !chain16_ok<NetR>(*d, params, 1)) return 0;
     if (NetR::HV == 4 ? (!gc->io.mean || !gc->io.value) : !gc->rp_log_std) return 0;
     hipLaunchKernelGGL((k_bptt_rollout<NetR, KIND, ACT, INTEG, DELAY>), dim3((N + 15) / 16), dim3(64), 0, st, d_dyn, d_env,

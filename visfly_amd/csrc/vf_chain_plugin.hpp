@@ -29,7 +29,8 @@ using ChainBackwardFn = int(const vf_mlp_bwd_desc* d, const float* packed, int M
 using PpoUpdateFn = int(const ChainArgs* g, const BwdArgsChain* gb, const PpoRowArgs* pr, int M, hipStream_t st);
 using TwinQUpdateFn = int(const ChainArgs* g, const BwdArgsChain* gb, const float* target, double* part, float scale, int M, hipStream_t st);
 // the persistent launches.  env_kind: the KERNEL-side kind (VF_ENV_RACING2 for RacingEnv2's 16-column rows); c: the host copy of the
-// dynamics constants; has_target: a second observation input was passed.  env_args / roll_args: vf::EnvArgs / vf::PpoRollArgs
+// dynamics constants; has_target: a second observation input was passed (the constant "target" rows; over a racing
+// kind the "gate" column, which the launch itself writes from step 1 on: PpoRollArgs / RollArgs::gate_slots).  env_args / roll_args: vf::EnvArgs / vf::PpoRollArgs
 // (vf_ppo_rollout_kernel.hpp), vf::EnvArgs / vf::RollArgs (vf_bptt_rollout_kernel.hpp); rev_args: vf::RevArgs (vf_bptt_reverse_kernel.hpp)
 using PpoRolloutFn = int(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
                          const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);

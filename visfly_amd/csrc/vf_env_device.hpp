@@ -162,8 +162,12 @@ constexpr int obs_width(int kind) { return kind == VF_ENV_RACING2 ? 16 : 13; }
 
 // the kernel-side env kinds a built-in actor class has persistent BPTT launches for (both halves): the one-observation classes over the
 // Hover, Navigation (NavigationEnv2: the target inside the "state" row) and Racing kinds, and over RacingEnv2's 16-column rows with the
-// motor lag only; the state + target classes over the Navigation kind
-constexpr bool bptt_instance(int NB, int kind, bool delay) { return NB == 2 ? kind == VF_ENV_NAV : kind != VF_ENV_RACING2 || delay; }
+// motor lag only; the two-observation classes over the Navigation kind (state + constant target rows) and over the racing kinds (state +
+// the gate column: StateGateExtractor), RacingEnv2's rows again with the motor lag only
+constexpr bool bptt_instance(int NB, int kind, bool delay)
+{
+    return NB == 2 ? kind == VF_ENV_NAV || kind == VF_ENV_RACING || (kind == VF_ENV_RACING2 && delay) : kind != VF_ENV_RACING2 || delay;
+}
 
 // the persistent launches' kernels are templates over the run-time configuration: f(kind, act, integ, delay) is called with the kernel-side
 // env kind, action type, integrator and motor-lag form as std::integral_constant values.  0: an env kind / action type without instances

@@ -123,7 +123,8 @@ __device__ __forceinline__ SpawnSlot load_spawn_slot(const EnvArgs& g, int i, bo
 template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false, int STRAIGHT = 0>
 __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_cfg& e, const EnvArgs& g, int i, bool live,
                                              Agent& s, Spares& sp, int wave_first, float* tile, float* reward_reg = nullptr,
-                                             bool* done_reg = nullptr, unsigned long long* tr = nullptr)   // tr: -DVF_ENV_TRACE builds only
+                                             bool* done_reg = nullptr, unsigned long long* tr = nullptr,   // tr: -DVF_ENV_TRACE builds only
+                                             int* gate_reg = nullptr)      // racing kinds: the agent's gate index after the step
 {
 #ifdef VF_ENV_TRACE
 #define VF_EPI_TR(k, x) do { if (tr) { asm volatile("" :: "v"(x) : "memory"); tr[k] = __builtin_amdgcn_s_memrealtime(); } } while (0)
@@ -299,6 +300,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
         race.y = __int_as_float(passed);
         *granule(g.d.S, g.d.G, i, g.g_race) = race;
         if (live && g.out.gate) g.out.gate[i] = gate;
+        if (gate_reg) *gate_reg = gate;             // (callers whose next policy forward reads the index: the persistent roll-outs)
     }
     pack_env(er, sp);
     VF_EPI_TR(9, sp.acc);                                                                // outputs written, re-spawn decided

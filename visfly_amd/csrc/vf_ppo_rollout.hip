@@ -21,7 +21,7 @@ namespace vf {
 // the roll-out of an actor-critic class (vf_chain_plugin.hpp: Builtin::ppo_rollout): the one-observation class over the Hover and
 // Navigation kinds (NavigationEnv2: the target is inside the "state" row) with either form of the interval, over RacingEnv's raw row and
 // RacingEnv2's 16 gate-relative columns (kernel-side kind VF_ENV_RACING2) with the motor lag; the state + target class over the
-// Navigation kind.  ROWS: the rows-per-wave choice of vf_mlp_forward for N rows (chain16_ok), so that the heads are the per-step path's
+// Navigation kind and, with the motor lag, over the racing kinds, where its second observation is the gate column (StateGateExtractor).  ROWS: the rows-per-wave choice of vf_mlp_forward for N rows (chain16_ok), so that the heads are the per-step path's
 // to the bit
 template <class Net, class NetPi>
 int Builtin<Net, NetPi>::ppo_rollout(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn,
@@ -31,10 +31,12 @@ int Builtin<Net, NetPi>::ppo_rollout(const vf_mlp_desc* d, int env_kind, const v
     const bool r16 = chain16_ok<Net>(*d, gc->params, N);
     const EnvArgs& ge = *static_cast<const EnvArgs*>(env_args);
     const PpoRollArgs& r = *static_cast<const PpoRollArgs*>(roll_args);
+    // a two-observation class over a racing kind reads the gate column (1 wide, rows written by the launch)
+    if (Net::NB == 2 && (env_kind == VF_ENV_RACING || env_kind == VF_ENV_RACING2) && (!r.gate_slots || d->in_dim[1] != 1)) return 0;
     return with_env_config(env_kind, *c, [&](auto kind, auto act, auto integ, auto delay) -> int {
         constexpr int K = decltype(kind)::value, A = decltype(act)::value, I = decltype(integ)::value;
         constexpr bool D = decltype(delay)::value;
-        if constexpr (Net::NB == 2 ? K == VF_ENV_NAV : K == VF_ENV_HOVER || K == VF_ENV_NAV || D) {
+        if constexpr (Net::NB == 2 ? K == VF_ENV_NAV || (kind_is_racing(K) && D) : K == VF_ENV_HOVER || K == VF_ENV_NAV || D) {
             if (r16) hipLaunchKernelGGL((k_ppo_rollout<Net, 16, K, A, I, D>), dim3((N + 15) / 16), dim3(64), 0, st, d_dyn, d_env, ge, *gc, r);
             else hipLaunchKernelGGL((k_ppo_rollout<Net, 32, K, A, I, D>), dim3((N + 31) / 32), dim3(64), 0, st, d_dyn, d_env, ge, *gc, r);
             VF_HIP(hipGetLastError());
@@ -54,7 +56,7 @@ extern "C" int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* p
 {
     if (!h || !desc || !params || !packed || !a || !a->out || !a->obs_state || !a->values || !a->actions || !a->log_probs || !a->rewards ||
         !a->episode_starts || !a->last_starts || !a->obs_final || !a->log_std || !a->cursor || !a->idx_list || !a->rows0 ||
-        !a->stat || a->T <= 0 || a->w1 < 0 || (a->w1 > 0 && (!a->rows1 || !a->obs_target_row)))
+        !a->stat || a->T <= 0 || a->w1 < 0 || (a->w1 > 0 && (!a->rows1 || !a->obs_target)))
         return vf::fail(VF_EINVAL, "vf_ppo_rollout: bad argument");
     const vf_env_out* out = a->out;
     if (!out->reward || !out->done || !out->ep_return || !out->ep_length || !out->ep_flags || !out->terminal_obs)
@@ -79,9 +81,15 @@ extern "C" int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* p
     ge.out.obs = T > 1 ? a->obs_state + (size_t)N * OW : a->obs_final;
     vf::ChainArgs gc{*desc, params, packed, vf::ChainIo{{a->obs_state, a->obs_target}, a->means, a->values}, T * N, nullptr, nullptr, nullptr,
                      {nullptr, nullptr}};
+    // a racing env's second observation is the gate column: its rows are written by the launch, obs_target_row is not read
+    const bool gate = h->cfg.kind == VF_ENV_RACING && a->w1 == 1;
+    if (a->w1 > 0 && !gate && !a->obs_target_row) return vf::fail(VF_EINVAL, "vf_ppo_rollout: obs_target_row is required with constant target rows");
     vf::PpoRollArgs r{T, N, reinterpret_cast<float4*>(a->actions), a->log_probs, a->rewards, a->episode_starts, a->last_starts,
                       a->obs_state, a->obs_final, a->log_std, a->noise_key, a->sample_step, a->obs_target_row, a->w1, a->capacity, a->cursor,
-                      a->idx_list, a->rows0, a->rows1, a->stat};
+                      a->idx_list, a->rows0, a->rows1, a->stat,
+                      // a racing env's second observation is the gate column (StateGateExtractor): obs_target = RolloutBuffer.obs["gate"],
+                      // [T][N][1], row 0 the caller's, the later rows written by the launch
+                      gate ? a->obs_target : nullptr};
     const int rc = vf::chain_serve("vf_ppo_rollout", true, &vf::ChainPlugin::ppo_rollout, desc, race2 ? vf::VF_ENV_RACING2 : h->cfg.kind, &h->dyn.cfg,
                                    a->obs_target != nullptr, h->dyn.d_cfg, h->d_cfg, &ge, &gc, &r, N, vf::as_stream(stream));
     if (rc < 0) return rc;

@@ -31,13 +31,21 @@ struct PpoRollArgs {
     float* rows0;                   // [capacity][13]
     float* rows1;                   // [capacity][w1]
     float* stat;                    // (N,4)
+    // racing kinds, two-branch class (StateGateExtractor): [T][N] = RolloutBuffer.obs["gate"], the gate index as a float column.  Row 0
+    // is the caller's, row t + 1 is written by step t; rows1 then takes the index the terminal "state" row was formed with.  Else null
+    float* gate_slots;
 };
+
+// branch 1 of a two-branch class over a racing kind is the gate column (one float: the index, exact), held by the wave -- not a row in memory
+template <class Net, int KIND>
+constexpr bool kGateBranch = Net::NB == 2 && kind_is_racing(KIND);
 
 // one forward of rows `row` (lane & (ROWS - 1) of the wave): value -> g.io.value; -> the mean row, valid in the lanes < ROWS
 // (the accumulator lanes of group 0 hold heads of their own row: chain_epilogue / chain16_epilogue).  The "state" row comes from
 // the wave's LDS tile (13 floats per agent, where the env epilogue of the previous step left it), other branches from memory.
-template <class Net, int ROWS, int OW = 13>
-__device__ __forceinline__ float4 policy_rows(const ChainArgs& gc, int lane, int row, const float* tile)
+// GATE: branch 1 is the gate column -- `gate` is the value of this lane's row (column 0 of an 8-wide fragment, the rest zero)
+template <class Net, int ROWS, int OW = 13, bool GATE = false>
+__device__ __forceinline__ float4 policy_rows(const ChainArgs& gc, int lane, int row, const float* tile, float gate = 0.0f)
 {
     const int m = lane & (ROWS - 1);
     if constexpr (ROWS == 16) {
@@ -48,6 +56,11 @@ __device__ __forceinline__ float4 policy_rows(const ChainArgs& gc, int lane, int
         for (int b = 0; b < Net::NB; ++b) {
             const int w = gc.d.in_dim[b];
             const float* x = b == 0 ? tile + m * OW : gc.io.in[b] + (size_t)row * w;
+            if (GATE && b == 1) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) st.x[b][j] = 4 * gq + j == 0 ? gate : 0.0f;
+                continue;
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = 4 * gq + j;
@@ -66,6 +79,11 @@ __device__ __forceinline__ float4 policy_rows(const ChainArgs& gc, int lane, int
         for (int b = 0; b < Net::NB; ++b) {
             const int w = gc.d.in_dim[b];
             const float* x = b == 0 ? tile + m * OW : gc.io.in[b] + (size_t)row * w;
+            if (GATE && b == 1) {
+#pragma unroll
+                for (int s = 0; s < Net::kin(b) / 2; ++s) st.x[b][s] = 2 * s + h == 0 ? gate : 0.0f;
+                continue;
+            }
 #pragma unroll
             for (int s = 0; s < Net::kin(b) / 2; ++s) {
                 const int k = 2 * s + h;
@@ -87,6 +105,7 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
     const vf_dyn_cfg& c = *cp;
     const vf_env_cfg& e = *ep;
     constexpr int OW = obs_width(KIND);       // 13, or RacingEnv2's 16 gate-relative columns (vf_env_device.hpp: race2_obs)
+    constexpr bool GATE = kGateBranch<Net, KIND>;
     __shared__ __attribute__((aligned(16))) float tile[64 * OW];
     const int lane = threadIdx.x, m = lane & (ROWS - 1);
     const int wave_first = blockIdx.x * ROWS;
@@ -105,6 +124,10 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
     // of step t + 1 there (store_rows_coalesced stages them through it on their way to RolloutBuffer.obs[t + 1]); step 0's come
     // from the caller's row 0.  One wave's LDS operations execute in order: no barrier.
     for (int k = 0; k < OW; ++k) tile[lane * OW + k] = r.obs_slots[(size_t)i * OW + k];
+    // the gate column of this lane's agent: row 0 is the caller's (the index its "state" row 0 was formed with); afterwards the index
+    // the epilogue leaves in a register -- every lane holds its own row's agent, replicas included, so nothing moves between lanes
+    float gate_col = 0.0f;
+    if constexpr (GATE) gate_col = r.gate_slots[i];
     __builtin_amdgcn_wave_barrier();
 #ifdef VF_PPO_TRACE
     long long tr[5] = {0, 0, 0, 0, 0}, tc = __builtin_readcyclecounter();
@@ -129,7 +152,7 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
         ChainArgs gct = gc;
         gct.packed = gc.packed + zero_t;
         gct.params = gc.params + zero_t;
-        float4 mean = policy_rows<Net, ROWS, OW>(gct, lane_t, row, tile);
+        float4 mean = policy_rows<Net, ROWS, OW, GATE>(gct, lane_t, row, tile, gate_col);
         // lane m < ROWS holds the head of its own agent; the replica lanes take it from there
         mean.x = __shfl(mean.x, m); mean.y = __shfl(mean.y, m); mean.z = __shfl(mean.z, m); mean.w = __shfl(mean.w, m);
         VF_PT(0);
@@ -156,7 +179,8 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
         VF_PT(2);
         float reward = 0.0f;
         bool done = false;
-        env_epilogue<KIND, false>(c, e, g, i, true, s, sp, wave_first, tile, &reward, &done);
+        int gate_next = 0;
+        env_epilogue<KIND, false>(c, e, g, i, true, s, sp, wave_first, tile, &reward, &done, nullptr, GATE ? &gate_next : nullptr);
         VF_PT(3);
         // ---- RolloutBuffer.add + the TimeLimit bookkeeping (k_rollout_post_collect) ----
         r.rewards[row] = reward;
@@ -178,9 +202,18 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
                     r.idx_list[slot] = row;
                     const float* to = g.out.terminal_obs + OW * (size_t)i;
                     for (int k = 0; k < OW; ++k) r.rows0[(size_t)slot * OW + k] = to[k];
-                    for (int k = 0; k < r.w1; ++k) r.rows1[(size_t)slot * r.w1 + k] = r.obs1[(size_t)i * r.w1 + k];
+                    if constexpr (GATE) {
+                        // the terminal "state" row carries the index of the step's start (terminal_gate): the column this step's forward read
+                        r.rows1[slot] = gate_col;
+                    } else {
+                        for (int k = 0; k < r.w1; ++k) r.rows1[(size_t)slot * r.w1 + k] = r.obs1[(size_t)i * r.w1 + k];
+                    }
                 }
             }
+        }
+        if constexpr (GATE) {       // RolloutBuffer.obs["gate"][t + 1] (the update reads it); the final observation's is the env's own buffer
+            gate_col = (float)gate_next;
+            if (t + 1 < r.T) r.gate_slots[(size_t)(t + 1) * r.N + i] = gate_col;
         }
         g.out.obs = t + 2 < r.T ? r.obs_slots + (size_t)(t + 2) * r.N * OW : r.obs_final;
         g.d.head = g.d.head + 1 == c.delay_steps ? 0 : g.d.head + 1;
@@ -197,7 +230,7 @@ __global__ __launch_bounds__(64) void k_ppo_rollout(const vf_dyn_cfg* __restrict
 namespace vf {
 
 // layout stamp of what a roll-out plugin is handed (vf_chain_plugin.hpp: ChainPlugin::rollout_abi)
-constexpr unsigned kRolloutPluginAbi = 0x52300002u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(PpoRollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
+constexpr unsigned kRolloutPluginAbi = 0x52300003u ^ (unsigned)(sizeof(EnvArgs) * 31u + sizeof(PpoRollArgs) * 17u + sizeof(vf_dyn_cfg) * 7u +
                                                                sizeof(vf_env_dev) * 5u + sizeof(ChainArgs) * 3u);
 
 }  // namespace vf
@@ -214,7 +247,9 @@ int plugin_ppo_rollout(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, 
                        const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st)
 {
     if (env_kind != KIND || c->action_type != ACT || c->integrator != INTEG || (c->ctrl_delay != 0) != DELAY) return 0;
-    if ((Net::NB == 2) != (has_target != 0) || (Net::NB == 2 && KIND != VF_ENV_NAV)) return 0;
+    // a second observation: the constant "target" rows over the Navigation kind, the gate column over the racing kinds
+    if ((Net::NB == 2) != (has_target != 0) || (Net::NB == 2 && KIND != VF_ENV_NAV && !kind_is_racing(KIND))) return 0;
+    if (kGateBranch<Net, KIND> && (!static_cast<const PpoRollArgs*>(roll_args)->gate_slots || d->in_dim[1] != 1)) return 0;
     if (!chain_matches_gen<Net>(*d)) return 0;
     hipLaunchKernelGGL((k_ppo_rollout<Net, 32, KIND, ACT, INTEG, DELAY>), dim3((N + 31) / 32), dim3(64), 0, st, d_dyn, d_env,
                        *static_cast<const EnvArgs*>(env_args), *gc, *static_cast<const PpoRollArgs*>(roll_args));

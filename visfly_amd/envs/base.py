@@ -856,7 +856,8 @@ class DroneGymEnvsBase:
     def rollout_policy(self, policy, obs_keys, eps, actions, d_reward, loss, disc, gamma, scale, reward_rows=None, ep_flag_rows=None):
         """H = eps.shape[0] closed-loop control steps -- policy forward (slots 0..H-1 of `policy`, reserved back to back), action
         head, state checkpoint on the tape, fused env step, loss / discount recurrence -- in ONE persistent launch
-        (vf_bptt_rollout).  Leaves exactly what H rounds of policy.forward_act + _step_no_grad(record=True) +
+        (vf_bptt_rollout).  obs_keys: "state", plus the constant "target" rows or, on the racing envs, the "gate" index column
+        (StateGateExtractor: the launch takes the index it holds after every step and writes it to the slots' "obs:gate").  Leaves exactly what H rounds of policy.forward_act + _step_no_grad(record=True) +
         vf_bptt_accumulate leave.  A policy with two 4-wide heads and no log_std parameter is the reference's own Actor
         (td_policies.py:146-252): state-dependent log_std, what H rounds of policy.forward + vf_shac_head_fwd leave, the heads of
         every step in the slots' "mean" / "value" buffers.  -> False when the library has no roll-out kernel for this env / network
@@ -872,7 +873,7 @@ class DroneGymEnvsBase:
         if t0 + H > self._tape.shape[0]:
             raise VisflyError("tape is full: call env.detach() (BPTT horizon exceeded)")
         nblk, blk = policy._slot_blocks.get(N, (0, None))
-        if nblk < H or any(k not in ("state", "target") for k in obs_keys):
+        if nblk < H or not self._persistent_keys_ok(obs_keys):
             return False
         obs = self.get_observation()
         blk["obs:state"][0].copy_(obs["state"].detach())
@@ -880,6 +881,11 @@ class DroneGymEnvsBase:
         if "target" in obs_keys:
             blk["obs:target"][:H].copy_(obs["target"].detach().unsqueeze(0).expand(H, N, -1))     # constant per env
             o1 = blk["obs:target"]
+        elif "gate" in obs_keys:
+            # the gate column (StateGateExtractor): slot 0 = the agents' current index, the one the "state" rows above were formed with
+            # (obs_gate_exact is False here); the launch writes the later slots from the index it holds after every step
+            blk["obs:gate"][0].copy_(obs["gate"].detach().reshape(N, 1))
+            o1 = blk["obs:gate"]
         b0 = policy._buffers(N, 0)
         key = (N, 0, True)
         d = policy._descs.get(key)
@@ -935,6 +941,13 @@ class DroneGymEnvsBase:
         policy._last_M, policy._last_slot = N, H - 1
         return True
 
+    def _persistent_keys_ok(self, obs_keys):
+        """observation keys the persistent launches take: "state", plus at most one of the constant "target" rows or -- racing envs
+        only -- the "gate" index column"""
+        keys = list(obs_keys)
+        return (all(k in ("state", "target", "gate") for k in keys) and not ("target" in keys and "gate" in keys)
+                and ("gate" not in keys or self.KIND == RACING))
+
     def _ensure_bptt_plugin(self, policy):
         """a generated actor class: the two persistent launches of its horizons are one more plugin, per env kind / action type /
         integrator / motor lag (visfly_amd/_jit.py: ensure_bptt; ~2 min of hipcc on first use, 16 agents per wave: N <= 16 384)"""
@@ -963,7 +976,7 @@ class DroneGymEnvsBase:
                 or self.envs.dynamics._wind_fn is not None or (getattr(self, "_HOST_OBS", False) and W == 13) or not self.tensor_output
                 or getattr(self, "obs_gate_exact", False)
                 or (W == 13 and self._terminal_state_rows() is not self._terminal_obs)
-                or any(k not in ("state", "target") for k in obs_keys) or policy._plan is None or not policy.fused
+                or not self._persistent_keys_ok(obs_keys) or policy._plan is None or not policy.fused
                 or policy.obs_dims.get("state") != W or buf.obs["state"].shape[-1] != W):
             return False
         assert self._is_initial, "You should call reset() before step()"
@@ -984,7 +997,8 @@ class DroneGymEnvsBase:
                 sc["terminal"] = th.zeros((N, W), dtype=th.float32, device=dev)
                 sc["out"].terminal_obs = _lib.ptr(sc["terminal"])
         final = th.empty((N, W), dtype=th.float32, device=dev)
-        o1 = buf.obs["target"] if "target" in obs_keys else None
+        # the second observation: the constant "target" rows, or the "gate" column (row 0 the caller's, the later rows the launch's)
+        o1 = buf.obs["target"] if "target" in obs_keys else buf.obs["gate"] if "gate" in obs_keys else None
         a = _lib.PpoRolloutArgs()
         a.T, a.w1, a.capacity = T, 0 if o1 is None else o1.shape[-1], boot["cap"]
         a.obs_state, a.obs_target = _lib.ptr(buf.obs["state"]), _lib.ptr(o1)

@@ -136,8 +136,8 @@ class RacingEnv(DroneGymEnvsBase):
     #    ignores its indices and rebuilds EVERY agent's observation (:347,460-469), now with the advanced / newly chosen gates;
     #  * RacingEnv.reset builds its observation inside super().reset(), before it re-chooses the gates (RacingEnv.py:165-170):
     #    the returned entry is the previous episode's (zeros on the first reset).
-    # `obs_gate_exact = False` (set by trainers whose policy does not read "gate") skips the two small launches this costs per
-    # step and returns the current index.
+    # `obs_gate_exact = False` (set by the trainers) skips the two small launches this costs per step and returns the current index:
+    # the one RacingEnv2's "state" rows are then formed with, and the one a policy that reads "gate" (StateGateExtractor) is fed.
     obs_gate_exact = True
     _g_obs = None
     _STATIC_OBS_CONST = False

@@ -2,8 +2,9 @@
 
 Restates the reference's PPO path (utils/algorithms/PPO.py:116-337 on top of SB3 2.2.1
 ``OnPolicyAlgorithm.collect_rollouts`` / ``RolloutBuffer``; policy = ``CustomMultiInputActorCriticPolicy``
-with ``StateExtractor`` / ``StateTargetExtractor`` MLPs, utils/policies/policies.py:195-254,
-utils/policies/extractors.py:376-449,578-592,662-678) with every arithmetic piece running as a HIP
+with ``StateExtractor`` / ``StateTargetExtractor`` / ``StateGateExtractor`` MLPs, utils/policies/policies.py:195-254,
+utils/policies/extractors.py:376-449,578-592,662-678,752-761; the last one reads the racing envs' "gate" index as one float column that
+holds the index the observation's "state" rows were formed with -- the agent's current gate, ``terminal_gate`` for a terminal row) with every arithmetic piece running as a HIP
 kernel behind the C-ABI: policy/value MLP forward + backward on the fp32 MFMA, squashed-Gaussian
 head sampling, GAE scan, advantage normalisation, clipped-surrogate loss, grad-norm clip + Adam.
 The rollout buffer lives on the device ([T][N] SoA); nothing crosses PCIe inside ``learn``.
@@ -41,6 +42,37 @@ LN_EPS = 1e-3
 # widest layer (in or out) of an MlpPolicy: the per-layer kernels' limit (vf_linear_*: K, No <= 512) / of a network the one-launch,
 # register-chained and persistent kernels can run (K, No <= 128: vf_linear_is_wide)
 MAX_WIDTH, FUSED_MAX_WIDTH = 512, 128
+
+
+# observation keys a trainer may feed its policy, and the ones among them that are integer indices: fed as one exact float32 column
+# (SB3's preprocess_obs is .float() for a Box space), never differentiated
+POLICY_OBS_KEYS = ("state", "target", "gate")
+INDEX_OBS_KEYS = ("gate",)
+
+
+def obs_width(t) -> int:
+    """columns of an observation entry as the policy reads it (RacingEnv's "gate" is (N,): one column)"""
+    return 1 if t.dim() == 1 else int(t.shape[1])
+
+
+def policy_rows(obs, keys):
+    """{key: the (N, w) contiguous float32 rows the policy reads} of an env observation.  "gate" (int32, (N,) from RacingEnv, (N, 1)
+    from RacingEnv2) becomes an (N, 1) float32 column holding the index exactly; float entries are passed as they are"""
+    out = {}
+    for k in keys:
+        t = obs[k].detach()
+        if k in INDEX_OBS_KEYS:
+            t = t.reshape(t.shape[0], -1).to(th.float32)
+        out[k] = t.contiguous()
+    return out
+
+
+def trainer_obs_keys(obs, policy_kwargs):
+    """the observation keys a trainer keeps: "state" and "target" as ever, "gate" only when the extractor the policy_kwargs name reads
+    it (StateGateExtractor / a native `extractor` dict with a "gate" branch)"""
+    avail = [k for k in obs.keys() if k in POLICY_OBS_KEYS]
+    named = checkpoint.extractor_keys(policy_kwargs, avail)
+    return [k for k in avail if k not in INDEX_OBS_KEYS or k in named]
 
 
 def activation_kind(a) -> int:
@@ -580,6 +612,8 @@ class MlpPolicy:
                 _lib.check(rc)
             if ly.first and not need_input_grad:
                 continue
+            if ly.first and ly.src[4:] in INDEX_OBS_KEYS:     # an index column carries no gradient: the branch stops at its first layer
+                continue
             if ly.first:
                 dX = d_in.setdefault(ly.src[4:], th.empty((M, ly.K), dtype=th.float32, device=self.device))
             else:
@@ -627,7 +661,9 @@ class MlpPolicy:
             if ly.first and not need_input_grad:
                 continue
             if ly.first:
-                dX = d_in.setdefault(ly.src[4:], th.empty((M, ly.K), dtype=th.float32, device=self.device))
+                # (an index column -- "gate" -- carries no gradient: the one-launch reverse kernels form every first layer's input tile
+                # or none, so its 1-wide tile goes to a buffer of its own that is never handed out)
+                dX = self._index_sink(M, ly.K) if ly.src[4:] in INDEX_OBS_KEYS else d_in.setdefault(ly.src[4:], th.empty((M, ly.K), dtype=th.float32, device=self.device))
             else:
                 dX = b["g:" + ly.src]
             key = (ly.src, ly.sc)
@@ -635,6 +671,14 @@ class MlpPolicy:
             touched.add(key)
         d.n_layers = n
         return d, d_in
+
+    def _index_sink(self, M, K):
+        """where the one-launch reverse kernels put the input tile of an index column: one buffer per row count, owned by the policy like its
+        other gradient buffers (dropped with them), never handed out"""
+        t = self._gbufs.get(("index_sink", M, K))
+        if t is None:
+            t = self._gbufs[("index_sink", M, K)] = th.empty((M, K), dtype=th.float32, device=self.device)
+        return t
 
     def forward_act(self, obs, eps, action, slot=0):
         """policy trunk + action head in one launch (vf_mlp_forward_act): ``action`` (M,4) <- tanh(mean + exp(log_std) eps),
@@ -1038,15 +1082,19 @@ class PPO:
         # TimeLimit bootstrap valued once per rollout (collect_rollouts) from the terminal rows the step kernel wrote; envs that
         # assemble their observation on the host (RacingEnv2: 16 gate-relative columns) have no such kernel rows -> valued per step
         self.defer_bootstrap, self._boot = (not getattr(env, "_HOST_OBS", False)) or getattr(env, "_OBS_W", 13) != 13, None
-        if hasattr(env, "obs_gate_exact"):       # RacingEnv / RacingEnv2: this policy does not read "gate"; its "state" rows use the agent's
-            env.obs_gate_exact = False           # current gate (what the persistent roll-out forms), as under BPTT / SHAC
+        if hasattr(env, "obs_gate_exact"):       # RacingEnv / RacingEnv2: the "state" rows use the agent's current gate (what the persistent
+            env.obs_gate_exact = False           # roll-out forms), as under BPTT / SHAC; a policy that reads "gate" (StateGateExtractor) is
+                                                 # fed that same index -- the one its "state" rows were formed with
         self.fused_rollout = True           # collect_rollouts as one persistent launch where the library has the kernel (vf_ppo_rollout)
         self._last_obs = None
         if not getattr(env, "_is_initial", False):
             self._last_obs = env.reset()
         obs = env.get_observation()
-        self.obs_keys = [k for k in obs.keys() if k in ("state", "target")]
-        obs_dims = {k: obs[k].shape[1] for k in self.obs_keys}
+        self.obs_keys = trainer_obs_keys(obs, policy_kwargs)
+        # the one key besides "state" (constant "target" rows, or the "gate" index column): what the bootstrap list's rows1 hold
+        self._key1 = next((k for k in self.obs_keys if k != "state"), None)
+        assert self._key1 in (None, "target", "gate")
+        obs_dims = {k: obs_width(obs[k]) for k in self.obs_keys}
         pk = checkpoint.policy_kwargs_from_reference(policy_kwargs, self.obs_keys)
         self.weight_decay = pk.get("weight_decay", self.weight_decay)   # optimizer_kwargs.weight_decay of the YAMLs
         extractor = pk.get("extractor", {k: [128, 64] for k in self.obs_keys})
@@ -1113,6 +1161,11 @@ class PPO:
     def lr(self, v):
         self.lr_schedule = v
 
+    def _terminal_gate_rows(self):
+        """(N, 1) float32: the gate index each agent's terminal "state" row was formed with (valid where the agent just ended an episode);
+        None for a policy without the gate branch"""
+        return self.env._terminal_gate.view(self.n_envs, 1).to(th.float32) if self._key1 == "gate" else None
+
     def _bootstrap_list(self):
         """compact list of the rollout's truncated rows (vf_rollout_post_collect): an agent is truncated at most once per
         max_episode_steps steps, plus the episode it is in when the rollout starts"""
@@ -1120,7 +1173,7 @@ class PPO:
             N, dev = self.n_envs, self.device
             per_agent = self.n_steps // max(int(getattr(self.env, "max_episode_steps", self.n_steps)), 1) + 2
             cap = (N * per_agent + 8191) // 8192 * 8192
-            w1 = self.policy.obs_dims.get("target", 0) if "target" in self.obs_keys else 0
+            w1 = self.policy.obs_dims[self._key1] if self._key1 else 0
             self._boot = {"cap": cap, "cursor": th.zeros(1, dtype=th.int32, device=dev), "idx": th.zeros(cap, dtype=th.int32, device=dev),
                           "rows0": th.zeros((cap, self.policy.obs_dims["state"]), device=dev),
                           "rows1": th.zeros((cap, w1), device=dev) if w1 else None,
@@ -1145,7 +1198,7 @@ class PPO:
     # ------------------------------------------------------------------------------------------
     def _act(self, obs, deterministic=False):
         """policy.forward (policies.py:195-226): action, value, log_prob"""
-        mean, value = self.policy.forward({k: obs[k] for k in self.obs_keys}, save_activations=False)
+        mean, value = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False)
         M = mean.shape[0]
         action = th.empty((M, 4), device=self.device)
         logp = th.empty(M, device=self.device)
@@ -1156,7 +1209,7 @@ class PPO:
         return action, value.view(M), logp
 
     def predict_values(self, obs):
-        _, value = self.policy.forward({k: obs[k] for k in self.obs_keys}, save_activations=False)
+        _, value = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False)
         return value.view(-1).clone()
 
     def predict(self, obs, state=None, episode_start=None, deterministic: bool = False):
@@ -1188,11 +1241,12 @@ class PPO:
         fused = False
         if replay is None and self.fused_rollout and self.defer_bootstrap and hasattr(env, "collect_policy"):
             # the whole loop below as one persistent launch (vf_ppo_rollout); same buffer rows, same Philox counters
+            rows = policy_rows(obs, self.obs_keys)
             for k in self.obs_keys:
-                if k == "state":
-                    buf.obs[k][0].copy_(obs[k])
+                if k == "target":
+                    buf.obs[k].copy_(rows[k].unsqueeze(0).expand_as(buf.obs[k]))       # constant per env
                 else:
-                    buf.obs[k].copy_(obs[k].unsqueeze(0).expand_as(buf.obs[k]))        # constant per env ("target")
+                    buf.obs[k][0].copy_(rows[k])          # ("gate": the launch writes the rows of the later steps, like "state")
             fused = env.collect_policy(pol, self.obs_keys, buf, bs, self._noise_key, self._sample_step, self._last_starts)
             if fused is not False:
                 obs = fused
@@ -1202,7 +1256,8 @@ class PPO:
         for t in range(self.n_steps if fused is False else 0):
             # policy.forward (policies.py:195-226) straight into row t of the buffer: value head, sampled action, log-prob
             action, logp = buf.actions[t], buf.log_probs[t]
-            mean, _ = pol.forward({k: obs[k] for k in self.obs_keys}, save_activations=False, out_value=buf.values[t])
+            rows = policy_rows(obs, self.obs_keys)
+            mean, _ = pol.forward(rows, save_activations=False, out_value=buf.values[t])
             self._sample_step += 1
             if replay is None:
                 _lib.check(L.vf_head_sample_at(_ptr(mean), _ptr(pol.log_std), _ptr(action), _ptr(logp), N, self._row0, self._noise_key,
@@ -1210,7 +1265,7 @@ class PPO:
             else:
                 _lib.check(L.vf_head_sample_eps(_ptr(mean), _ptr(pol.log_std), _ptr(r_eps[t]), _ptr(action), _ptr(logp), N, self._stream()))
             for k in self.obs_keys:
-                buf.obs[k][t].copy_(obs[k])
+                buf.obs[k][t].copy_(rows[k])
             obs, reward, done, _info = env.step(action if replay is None else r_act[t])
             if not self.defer_bootstrap:
                 _lib.check(L.vf_episode_stats(done.data_ptr(), _ptr(env._ep_return), _ptr(env._ep_length), _ptr(env._ep_flags),
@@ -1221,7 +1276,9 @@ class PPO:
             trows = env._terminal_state_rows()               # (N, w) in the env's observation map, w = the policy's row width
             assert trows.shape[1] == pol.obs_dims["state"], (trows.shape, pol.obs_dims)
             if self.defer_bootstrap:
-                o1 = obs["target"] if "target" in self.obs_keys else None
+                # the second entry of a truncated agent's terminal observation: its constant "target" row, or the gate index its terminal
+                # "state" row was formed with (terminal_gate)
+                o1 = obs["target"] if self._key1 == "target" else self._terminal_gate_rows()
                 _lib.check(L.vf_rollout_post_collect(_ptr(reward), done.data_ptr(), _ptr(env._ep_flags), _ptr(buf.rewards[t]), _ptr(nxt),
                                                      _ptr(trows), _ptr(o1), trows.shape[1], 0 if o1 is None else o1.shape[1],
                                                      bs["cursor"].data_ptr(), bs["cap"], bs["idx"].data_ptr(), _ptr(bs["rows0"]),
@@ -1229,8 +1286,10 @@ class PPO:
                                                      _ptr(bs["stat"]), self._stream()))
             else:
                 tobs = {"state": trows.contiguous()}
-                if "target" in self.obs_keys:
+                if self._key1 == "target":
                     tobs["target"] = obs["target"]
+                elif self._key1 == "gate":
+                    tobs["gate"] = self._terminal_gate_rows()
                 _, tv = pol.forward(tobs, save_activations=False)
                 _lib.check(L.vf_rollout_post(_ptr(reward), done.data_ptr(), _ptr(env._ep_flags), _ptr(tv), float(self.gamma),
                                              _ptr(buf.rewards[t]), _ptr(nxt), N, self._stream()))
@@ -1244,7 +1303,7 @@ class PPO:
                 m = min(CH, cnt - s0)
                 rows = {"state": bs["rows0"][s0:s0 + CH]}
                 if bs["rows1"] is not None:
-                    rows["target"] = bs["rows1"][s0:s0 + CH]
+                    rows[self._key1] = bs["rows1"][s0:s0 + CH]
                 _, tv = pol.forward(rows, save_activations=False)
                 _lib.check(L.vf_bootstrap_scatter(bs["idx"].data_ptr() + 4 * s0, _ptr(tv), m, float(self.gamma), _ptr(buf.rewards),
                                                   self._stream()))

@@ -29,6 +29,11 @@ ContinuousCritic / StateExtractor / create_mlp / SimpleRolloutBuffer / compute_t
 (``oracle/gen_shac.py``; SB3's base classes restated there, reference defect C-10 repaired: the buffer's observations are
 flattened like its actions): horizon buffer, next values, actor loss incl. bootstrap, flat actor gradient, actor parameters after
 the step, returns, and per critic step loss / gradient / parameters / target parameters (``tests/test_shac_gpu.py``).
+
+Extractors: ``StateExtractor``, ``StateTargetExtractor`` and, on the racing envs, ``StateGateExtractor`` (the "gate" index as one float
+column: bptt.py).  The actor's horizons run on the persistent launches with the gate branch; the twin critic over a two-branch extractor
+keeps running on the block-tile kernels (visfly_amd/_jit.py: a generated critic class has one branch) -- an existing limit, not part of
+the gate branch.
 """
 import ctypes as C
 from typing import Optional
@@ -37,7 +42,7 @@ import torch as th
 
 from . import _lib, checkpoint, parallel
 from .bptt import BPTT, LOG_STD_MAX, LOG_STD_MIN
-from .ppo import MlpPolicy, _ptr
+from .ppo import MlpPolicy, _ptr, policy_rows
 
 
 class SHAC(BPTT):
@@ -150,8 +155,7 @@ class SHAC(BPTT):
             for k in keys:
                 b["obs"][k].copy_(blk["obs:" + k][:H])                                 # rollout_buffer.add(obs=pre_obs ...) :259
             b["done"].copy_(env._tape_done[t0:t0 + H])
-            last = env.get_observation()
-            o_last = {k: last[k].detach().contiguous() for k in keys}
+            o_last = policy_rows(env.get_observation(), keys)
             mu2, ls2, nxt = th.empty((H, N, 4), **f), th.empty((H, N, 4), **f), th.empty((H, N, 4), **f)
             if H > 1:
                 mu2[:H - 1].copy_(blk["mean"][1:H])
@@ -183,17 +187,17 @@ class SHAC(BPTT):
                                                 b["ep_done"][t].data_ptr(), float(self.gamma), scale, 1 if t == H - 1 else 0, N, st))
         else:
             nxt = th.empty((N, 4), **f)
-            obs = env.get_observation()
+            obs = policy_rows(env.get_observation(), keys)
         for t in range(0 if not fused else H, H):
             for k in keys:
-                b["obs"][k][t].copy_(obs[k].detach())                                  # rollout_buffer.add(obs=pre_obs ...) :259
+                b["obs"][k][t].copy_(obs[k])                                  # rollout_buffer.add(obs=pre_obs ...) :259
             o = {k: b["obs"][k][t] for k in keys}                                      # rows that outlive the reverse sweep
             mu, ls = pol.forward(o, slot=t)                                            # actor.action_log_prob(obs) :219
             action = b["action"][t]
             self._head_fwd(mu, ls, eps_a[t], action)
             obs, reward, done, _ = env._step_no_grad(action, False, record=True, borrow=True)      # :225
             # next action of the stochastic actor on the new observation, target critics on (obs', a'), all detached :234-239
-            o2 = {k: obs[k].detach().contiguous() for k in keys}
+            obs = o2 = policy_rows(obs, keys)
             mu2, ls2 = pol.forward(o2, save_activations=False, slot=H)
             self._head_fwd(mu2, ls2, eps[2 * t + 1], nxt)
             q0, q1 = self._q(self.critic_target, o2, nxt, slot=0)
@@ -303,7 +307,7 @@ class SHAC(BPTT):
     def predict(self, obs, state=None, episode_start=None, deterministic: bool = False):
         """shac.py:334-343 / MTDPolicy.predict: -> (action, None); deterministic: tanh(mu)"""
         N = obs[self.obs_keys[0]].shape[0]
-        mu, ls = self.policy.forward({k: obs[k].detach().contiguous() for k in self.obs_keys}, save_activations=False, slot=self.H + 1)
+        mu, ls = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1)
         if deterministic:
             return th.tanh(mu), None
         eps = self._noise(1, N)[0]
