@@ -1004,6 +1004,14 @@ int64_t vf_twin_q_update_scratch_doubles(int32_t M);
 int vf_twin_q_update(const vf_mlp_desc* fwd, const vf_mlp_bwd_desc* bwd, const float* params, const float* packed, const float* in0,
                      const float* in1, const float* target, float* loss_out, double* scratch, int32_t M, int64_t M_global,
                      vf_stream_t stream);
+/* vf_twin_q_update_in3 the same step with a third input pointer, for a twin critic over a TWO-branch extractor (StateTargetExtractor,
+ *                       StateGateExtractor): in0 / in1 = the observation rows of the two branches, in2 = the action rows.  in2 == NULL:
+ *                       exactly vf_twin_q_update (in1 = the action rows).  Same tables, same buffers left behind, same scratch, same
+ *                       return codes; the classes that serve three inputs are generated ones (heads 1 / 1, one pass-through input of
+ *                       <= 4 columns behind two branches, features (+) action <= 128 columns).  No ABI bump: nothing existing changes. */
+int vf_twin_q_update_in3(const vf_mlp_desc* fwd, const vf_mlp_bwd_desc* bwd, const float* params, const float* packed, const float* in0,
+                         const float* in1, const float* in2, const float* target, float* loss_out, double* scratch, int32_t M,
+                         int64_t M_global, vf_stream_t stream);
 int vf_polyak_update(float* target, const float* param, int64_t n, double tau, vf_stream_t stream);
 
 /* test hook: fills the LDS of every CU with NaNs (tests/test_shac_gpu.py: layer tables with widths that are not multiples of

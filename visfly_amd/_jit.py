@@ -10,8 +10,10 @@ the GPU box finds them in the snapshot.
 
 Shapes that qualify: 1-2 observation branches of <= 32 columns (the second one: NavigationEnv's constant "target" rows, or the racing envs'
 1-wide "gate" column, which the persistent launches of a racing kind take from the index the wave holds instead of from memory), 1-4 layers per branch / trunk, widths in multiples of 32 up to 128,
-the actor-critic heads (4, 1), the SAC-style Actor's (4, 4), or the twin critic's (1, 1) with its pass-through action input behind ONE
-observation branch.  Everything else keeps running on the block-tile kernels (MlpPolicy warns once).
+the actor-critic heads (4, 1), the SAC-style Actor's (4, 4), or the twin critic's (1, 1) with its pass-through action input (<= 4 columns)
+behind one or two observation branches, as long as features (+) action fit the trunks' 128 input columns (the pass-through tile counts as
+one of the four: sum of the branches' last widths + action columns <= 128; the reference-default two-branch critic, 64 + 64 + 4 = 132
+columns, does not qualify).  Everything else keeps running on the block-tile kernels (MlpPolicy warns once).
 ``VISFLY_AMD_JIT=0`` switches the compilation off.
 
 Two more plugin kinds hold ONE instance each of a persistent launch for a generated class under one env kind / action type / integrator /
@@ -76,6 +78,11 @@ PREBUILD_ACT = {
 PREBUILD_CRITIC = {
     "critic_hover": ({"state": 13, "action": 4}, {"state": [64, 64, 32]}, [32], [32], (1, 1), ("action",)),      # SHAC(net_arch pi=[32]) over features [64, 64, 32]
     "critic_wide": ({"state": 13, "action": 4}, {"state": [128, 96]}, [128, 64], [128, 64], (1, 1), ("action",)),
+    # ... over a two-branch extractor (NB = 2 with PASS; feature tiles in the order branch 0, branch 1, action):
+    # the critic SHAC builds next to PREBUILD_SAC["gate_sac"] (StateGateExtractor on the racing envs; the gate column is branch 1, KIN 8)
+    "critic_gate": ({"state": 16, "gate": 1, "action": 4}, {"state": [64, 32], "gate": [32]}, [32], [32], (1, 1), ("action",)),
+    # ... and next to "sac_nav_bptt" (StateTargetExtractor on NavigationEnv): 64 + 32 + 4 = 100 columns into qf0 / qf1
+    "critic_nav": ({"state": 13, "target": 3, "action": 4}, {"state": [64, 64], "target": [32]}, [64], [64], (1, 1), ("action",)),
 }
 PREBUILD_SAC = {
     "sac_nav": ({"state": 13, "target": 3}, {"state": [128, 64], "target": [64]}, [128, 64], [64], (4, 4)),
@@ -105,7 +112,10 @@ def shape_of(obs_dims, extractor, pi, vf, head_dims=(4, 1), passthrough=(), acts
     critic = tuple(head_dims) == (1, 1)      # td_policies.ContinuousCritic: th.cat([features, actions]) -> qf0 / qf1 (one pass-through input of <= 4 columns)
     if critic != bool(passthrough) or tuple(head_dims) not in ((4, 1), (4, 4), (1, 1)) or not 1 <= len(extractor) <= 2:
         return None
-    if critic and (len(passthrough) != 1 or len(extractor) != 1 or not 1 <= int(obs_dims[list(passthrough)[0]]) <= 4):
+    if critic and (len(passthrough) != 1 or not 1 <= int(obs_dims[list(passthrough)[0]]) <= 4):
+        return None
+    # features (+) pass-through columns are the K of the trunks' first layers: at most 128 (four input tiles, the pass-through tile included)
+    if critic and sum(int(h[-1]) for h in extractor.values() if h) + int(obs_dims[list(passthrough)[0]]) > 128:
         return None
     kin, ew = [], []
     for k, hidden in extractor.items():
@@ -353,11 +363,11 @@ def ensure_bptt(shape, cfg):
 
 
 def prebuild_shape(name):
-    """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC, or of PREBUILD_ACT (with its activations)"""
+    """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC / PREBUILD_CRITIC, or of PREBUILD_ACT (with its activations)"""
     if name in PREBUILD_ACT:
         v = PREBUILD_ACT[name]
         return shape_of(*v[:5], acts=v[5])
-    return shape_of(*{**PREBUILD, **PREBUILD_SAC}[name])
+    return shape_of(*{**PREBUILD, **PREBUILD_SAC, **PREBUILD_CRITIC}[name])
 
 
 def prebuild(verbose=False):

@@ -225,6 +225,7 @@ SIGNATURES = {
     "vf_mlp_forward_steps": (C.c_int, [C.POINTER(MlpDesc)] + [_vp] * 7 + [C.c_int32, C.c_int32, _vp]),
     "vf_twin_q_update_scratch_doubles": (C.c_int64, [C.c_int32]),
     "vf_twin_q_update": (C.c_int, [C.POINTER(MlpDesc), C.POINTER(MlpBwdDesc)] + [_vp] * 7 + [C.c_int32, C.c_int64, _vp]),
+    "vf_twin_q_update_in3": (C.c_int, [C.POINTER(MlpDesc), C.POINTER(MlpBwdDesc)] + [_vp] * 8 + [C.c_int32, C.c_int64, _vp]),
     "vf_polyak_update": (C.c_int, [_vp, _vp, C.c_int64, C.c_double, _vp]),
     "vf_debug_poison_lds": (C.c_int, [_vp]),
     "vf_bptt_reverse": (C.c_int, [_vp, C.POINTER(MlpBwdDesc)] + [_vp] * 5 + [C.c_int64] + [_vp] * 6 + [C.c_int32, _vp, _vp, _vp]),

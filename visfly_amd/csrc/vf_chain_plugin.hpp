@@ -21,7 +21,8 @@ constexpr unsigned kChainPluginAbi = 0x56460005u ^ (unsigned)(sizeof(vf_mlp_desc
                                                             sizeof(BwdArgsChain) * 5u + sizeof(PpoRowArgs) * 3u + sizeof(ReparamFwd) + sizeof(ReparamBwd));
 
 // out1 == null: the policy-only class (no value trunk).  M_choice > 0: the rows-per-wave choice is made for M_choice rows
-// (vf_mlp_forward_steps).  in2: a third input (a plugin class has none: it answers 0)
+// (vf_mlp_forward_steps).  in2: a third input -- the pass-through rows of a twin critic over two observation branches; a class with fewer
+// inputs answers 0 when it is set
 using ChainForwardFn = int(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1, const float* in2,
                            float* out0, float* out1, int M, hipStream_t st, const ReparamFwd* rp, int M_choice);
 // packed == null: capability query
@@ -119,10 +120,11 @@ template <class Net, class NetPi>
 int plugin_forward(const vf_mlp_desc* d, const float* params, const float* packed, const float* in0, const float* in1, const float* in2, float* out0,
                    float* out1, int M, hipStream_t st, const ReparamFwd* rpp, int M_choice)
 {
-    if ((Net::NB + Net::PASS == 2 && !in1) || in2) return 0;
+    constexpr int n_in = Net::NB + Net::PASS;      // observation branches, then the pass-through input (ChainIo::in)
+    if ((n_in >= 2 && !in1) || (n_in == 3 ? !in2 : in2 != nullptr)) return 0;
     const ReparamFwd rp = rpp ? *rpp : ReparamFwd{};
     if (Net::PASS && (rpp || !out0 || !out1)) return 0;      // the twin critic: Q1 / Q2 (M,), no action head
-    ChainArgs g{*d, params, packed, ChainIo{{in0, in1, nullptr}, out0, out1}, M, rp.log_std, reinterpret_cast<const float4*>(rp.eps),
+    ChainArgs g{*d, params, packed, ChainIo{{in0, in1, n_in == 3 ? in2 : nullptr}, out0, out1}, M, rp.log_std, reinterpret_cast<const float4*>(rp.eps),
                 reinterpret_cast<float4*>(rp.action), {rp.obs_copy[0], rp.obs_copy[1]}};
     if (!out1) {
         if constexpr (Net::HV != 1 || Net::HM != 4) {
@@ -212,7 +214,10 @@ int plugin_twin_q_update(const ChainArgs* g, const BwdArgsChain* gb, const float
         return 0;
     } else {
         using PU = typename Net::template Bwd<true, true, false>;
-        if (!g->io.in[1] || !chain_matches_gen<Net>(g->d) || !bwd_chain_matches_gen<PU>(gb->d, false)) return 0;
+        for (int b = 0; b <= Net::NB; ++b)      // the branches' observation rows, then the pass-through rows (chain_pass_tile: io.in[NB])
+            if (!g->io.in[b]) return 0;
+        if (Net::NB == 1 && g->io.in[2]) return 0;
+        if (!chain_matches_gen<Net>(g->d) || !bwd_chain_matches_gen<PU>(gb->d, false)) return 0;
         hipLaunchKernelGGL(k_twin_q_update_chain<Net>, dim3((M + 31) / 32), dim3(64), 0, st, *g, *gb, target, part, scale);
         VF_HIP(hipGetLastError());
         return 1;

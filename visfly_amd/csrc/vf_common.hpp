@@ -247,9 +247,10 @@ int mlp_forward_chain_try(const vf_mlp_desc* d, const float* params, const float
                           int M_choice = 0);      // M_choice > 0: rows-per-wave choice as for M_choice rows (vf_mlp_forward_steps)
 // reverse chain (data gradients); packed == nullptr: capability query
 int mlp_backward_chain_try(const vf_mlp_bwd_desc* d, const float* packed, int M, hipStream_t st, const ReparamBwd* rp = nullptr);
-// fused critic step of SHAC (forward + twin-Q loss + reverse chain) for the twin critic's classes
+// fused critic step of SHAC (forward + twin-Q loss + reverse chain) for the twin critic's classes; in2: the pass-through rows of a critic
+// over two observation branches, else null
 int twin_q_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const float* params, const float* packed, const float* in0,
-                            const float* in1, const float* target, double* part, float scale, int M, hipStream_t st);
+                            const float* in1, const float* in2, const float* target, double* part, float scale, int M, hipStream_t st);
 // fused PPO minibatch step (forward + loss + reverse chain) for the actor-critic classes
 int ppo_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const float* params, const float* packed, const float* in0,
                          const float* in1, const float* log_std, const float* action, const float* old_lp, const float* adv,

@@ -91,9 +91,10 @@ int ppo_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const 
     return chain_serve("vf_ppo_update", true, &ChainPlugin::ppo_update, &g, &gb, &pr, M, st);
 }
 
-// fused critic step (forward + twin-Q loss + reverse chain): 1 launched, 0 no class serves it, < 0 error.  part: ceil(M / 32) doubles
+// fused critic step (forward + twin-Q loss + reverse chain): 1 launched, 0 no class serves it, < 0 error.  part: ceil(M / 32) doubles.
+// in2: the pass-through rows of a critic over two observation branches (in0 / in1), else null (in1 = the pass-through rows)
 int twin_q_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, const float* params, const float* packed, const float* in0,
-                            const float* in1, const float* target, double* part, float scale, int M, hipStream_t st)
+                            const float* in1, const float* in2, const float* target, double* part, float scale, int M, hipStream_t st)
 {
     for (int i = 0; i < d->n_layers; ++i)
         if (d->layer[i].dst < VF_MLP_OUT0 && !d->layer[i].save && !((d->identity_mask >> i) & 1)) return 0;   // the weight gradients need every layer input
@@ -101,7 +102,7 @@ int twin_q_update_chain_try(const vf_mlp_desc* d, const vf_mlp_bwd_desc* bd, con
         if (d->layer[i].save && !rows_fit_u32(M, d->layer[i].save_ld)) return 0;
     for (int l = 0; l < bd->n_layers; ++l)
         if (!rows_fit_u32(M, bd->layer[l].ld_dy)) return 0;
-    const ChainArgs g{*d, params, packed, ChainIo{{in0, in1}, nullptr, nullptr}, M, nullptr, nullptr, nullptr, {nullptr, nullptr}};
+    const ChainArgs g{*d, params, packed, ChainIo{{in0, in1, in2}, nullptr, nullptr}, M, nullptr, nullptr, nullptr, {nullptr, nullptr}};
     const BwdArgsChain gb{*bd, packed, M, nullptr, nullptr, nullptr, nullptr, nullptr};
     return chain_serve("vf_twin_q_update", true, &ChainPlugin::twin_q_update, &g, &gb, target, part, scale, M, st);
 }

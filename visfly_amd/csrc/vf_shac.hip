@@ -252,21 +252,28 @@ int vf_twin_q_loss(const float* q0, const float* q1, const float* target, float*
 
 int64_t vf_twin_q_update_scratch_doubles(int32_t M) { return M > 0 ? (M + 31) / 32 : 0; }
 
-int vf_twin_q_update(const vf_mlp_desc* fwd, const vf_mlp_bwd_desc* bwd, const float* params, const float* packed, const float* in0,
-                     const float* in1, const float* target, float* loss_out, double* scratch, int32_t M, int64_t M_global,
-                     vf_stream_t stream)
+int vf_twin_q_update_in3(const vf_mlp_desc* fwd, const vf_mlp_bwd_desc* bwd, const float* params, const float* packed, const float* in0,
+                         const float* in1, const float* in2, const float* target, float* loss_out, double* scratch, int32_t M,
+                         int64_t M_global, vf_stream_t stream)
 {
     if (!fwd || !bwd || !params || !packed || !in0 || !in1 || !target || !loss_out || !scratch || M <= 0 || M_global < M)
         return vf::fail(VF_EINVAL, "vf_twin_q_update: bad argument");
     if (fwd->n_layers < 1 || fwd->n_layers > VF_MLP_MAX_LAYERS || bwd->n_layers < 1 || bwd->n_layers > VF_MLP_MAX_LAYERS)
         return vf::fail(VF_EINVAL, "vf_twin_q_update: bad layer count");
     hipStream_t st = vf::as_stream(stream);
-    const int rc = vf::twin_q_update_chain_try(fwd, bwd, params, packed, in0, in1, target, scratch, (float)(1.0 / (double)M_global), M, st);
+    const int rc = vf::twin_q_update_chain_try(fwd, bwd, params, packed, in0, in1, in2, target, scratch, (float)(1.0 / (double)M_global), M, st);
     if (rc < 0) return rc;
     if (rc == 0) return vf::fail(VF_EUNSUPPORTED, "vf_twin_q_update: the layer tables are not the instantiated twin-critic class");
     hipLaunchKernelGGL(vf::k_twin_q_fold_wide, dim3(1), dim3(1024), 0, st, scratch, (M + 31) / 32, loss_out, 1.0 / (double)M_global);
     VF_HIP(hipGetLastError());
     return VF_OK;
+}
+
+int vf_twin_q_update(const vf_mlp_desc* fwd, const vf_mlp_bwd_desc* bwd, const float* params, const float* packed, const float* in0,
+                     const float* in1, const float* target, float* loss_out, double* scratch, int32_t M, int64_t M_global,
+                     vf_stream_t stream)
+{
+    return vf_twin_q_update_in3(fwd, bwd, params, packed, in0, in1, nullptr, target, loss_out, scratch, M, M_global, stream);
 }
 
 int vf_polyak_update(float* target, const float* param, int64_t n, double tau, vf_stream_t stream)

@@ -916,10 +916,10 @@ class MlpPolicy:
 
     def twin_q_update(self, obs, target, loss_out, m_global):
         """a twin critic's update step up to the flat gradient (shac.py:267-270): forward + mse_loss(target, min(Q1, Q2)) + reverse
-        chain in one launch (vf_twin_q_update), then the weight gradients into ``self.grad``.  ``obs``: the extractor's observations
-        + the pass-through "action" rows; ``loss_out`` (1,) device tensor.  -> False when the network is not the register-chained
+        chain in one launch (vf_twin_q_update / vf_twin_q_update_in3), then the weight gradients into ``self.grad``.  ``obs``: the
+        observations of the extractor's one or two branches + the pass-through "action" rows; ``loss_out`` (1,) device tensor.  -> False when the network is not the register-chained
         critic class (the caller then runs forward / vf_twin_q_loss / backward)."""
-        if self._fused_twin_q is False or self._plan is None or not (self.fused and self.fused_backward) or len(self.obs_keys) != 2:
+        if self._fused_twin_q is False or self._plan is None or not (self.fused and self.fused_backward) or len(self.obs_keys) not in (2, 3):
             return False
         M = target.shape[0]
         b = self._buffers(M, 0)
@@ -949,8 +949,9 @@ class MlpPolicy:
         for i, src in firsts:                 # entries whose X is an observation: the caller's tensor, may change from call to call
             bd.layer[i].X = _ptr(b[src])
         self._pack()
-        rc = L.vf_twin_q_update(C.byref(d), C.byref(bd), _ptr(self.flat), _ptr(self._packed), _ptr(b["obs:" + self.obs_keys[0]]),
-                                _ptr(b["obs:" + self.obs_keys[1]]), _ptr(target), _ptr(loss_out), scr.data_ptr(), M, int(m_global), st)
+        ins = [_ptr(b["obs:" + k]) for k in self.obs_keys] + [None] * (3 - len(self.obs_keys))      # (two branches: the action rows are in2)
+        rc = L.vf_twin_q_update_in3(C.byref(d), C.byref(bd), _ptr(self.flat), _ptr(self._packed), ins[0], ins[1], ins[2], _ptr(target),
+                                    _ptr(loss_out), scr.data_ptr(), M, int(m_global), st)
         if rc == _lib.EUNSUPPORTED:
             self._fused_twin_q = False
             self._warn_fallback("vf_twin_q_update")

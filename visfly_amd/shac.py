@@ -32,8 +32,9 @@ the step, returns, and per critic step loss / gradient / parameters / target par
 
 Extractors: ``StateExtractor``, ``StateTargetExtractor`` and, on the racing envs, ``StateGateExtractor`` (the "gate" index as one float
 column: bptt.py).  The actor's horizons run on the persistent launches with the gate branch; the twin critic over a two-branch extractor
-keeps running on the block-tile kernels (visfly_amd/_jit.py: a generated critic class has one branch) -- an existing limit, not part of
-the gate branch.
+is a generated chain class like the one-branch critic (visfly_amd/_jit.py: features (+) action <= 128 columns), its update the fused
+step (vf_twin_q_update_in3: the action rows are the third input).  The reference-default two-branch extractor ([128, 64] x 2: 132
+columns into qf0 / qf1) still runs layer by layer.
 """
 import ctypes as C
 from typing import Optional
