@@ -959,6 +959,41 @@ typedef struct vf_ppo_rollout_args {
 int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* params, const float* packed, const vf_ppo_rollout_args* a,
                    vf_stream_t stream);
 
+/* Deterministic evaluation episodes (the reference's eval loop: utils/algorithms/BPTT.py:138-156, shac.py:284-300,
+ * utils/evaluate.py:79-129): a = tanh(mean(obs)) -> env step with is_test (no re-spawn, `done` sticky) until every agent has finished
+ * one episode, T_max = max_episode_steps steps at the latest, as ONE persistent launch of the vf_ppo_rollout kind.  An agent's episode
+ * is what the env step reported at the FIRST step that set its `done`: the launch copies ep_return / ep_length / ep_flags (and the
+ * terminal row) of that step to the latched outputs, once; rows-per-wave as vf_mlp_forward (both heads) chooses for N rows, so the
+ * results equal T_max rounds of vf_mlp_forward + vf_eval_action + vf_env_step(auto_reset = 0) + vf_eval_latch bit for bit
+ * (tests/test_evaluate_gpu.py).  A wave leaves the loop once all its agents are latched: afterwards the slab does NOT hold what T_max
+ * per-step launches leave -- every agent is done on either path and the env must be reset (vf_env_reset, all agents) before it is
+ * stepped again.  Serves the classes with a 4-wide mean head (actor-critic: PPO / the one-head BPTT actor; the SAC-style Actor: only mu
+ * is read; generated classes through their evaluation plugin) over the configurations of vf_ppo_rollout; VF_EUNSUPPORTED otherwise.
+ * Advances the delay-ring phase by T_max.  desc: the layer table WITHOUT activation copies. */
+typedef struct vf_eval_rollout_args {
+    int32_t T_max, w1;
+    const float* obs_state;     /* (N,13) -- RacingEnv2: (N,16) -- the observation after the reset */
+    const float* obs_second;    /* (N,w1) constant "target" rows; racing env with w1 = 1: the "gate" column of obs_state (row 0; the launch
+                                   keeps the index afterwards); or NULL */
+    float* obs_scratch;         /* (N,13|16) the next observation of every step, overwritten step by step */
+    float* ep_return;           /* (N,) latched outputs: rows of agents that never finish keep their content (cannot happen with */
+    int32_t* ep_length;         /* (N,)   T_max >= max_episode_steps after a reset) */
+    uint8_t* ep_flags;          /* (N,) VF_EP_* */
+    float* terminal_rows;       /* (N,13|16) the terminal observation rows, or NULL */
+    const vf_env_out* out;      /* the env's own episode outputs (all of ep_return / ep_length / ep_flags / terminal_obs) and reward /
+                                   done scratch of N elements; obs ignored */
+} vf_eval_rollout_args;
+int vf_eval_rollout(vf_env* h, const vf_mlp_desc* desc, const float* params, const float* packed, const vf_eval_rollout_args* a,
+                    vf_stream_t stream);
+/* The latch of the launch-by-launch loop, after every vf_env_step(auto_reset = 0): for the agents with done[i] != 0 and latched[i] == 0,
+ * out_* [i] = the step's episode outputs (out_terminal / terminal_obs: (N,OW) rows or both NULL) and latched[i] = 1.  Elementwise. */
+int vf_eval_latch(const uint8_t* done, const float* ep_return, const int32_t* ep_length, const uint8_t* ep_flags,
+                  const float* terminal_obs, uint8_t* latched, float* out_return, int32_t* out_length, uint8_t* out_flags,
+                  float* out_terminal, int32_t N, int32_t OW, vf_stream_t stream);
+/* action (N,4) = tanhf(mean (N,4)): the deterministic action of either actor kind, with the device function vf_eval_rollout evaluates
+ * (vf_head_sample with deterministic = 1 is the same arithmetic but needs a log_std parameter row, which the SAC-style Actor has not) */
+int vf_eval_action(const float* mean, float* action, int32_t N, vf_stream_t stream);
+
 /* ---- SHAC (utils/algorithms/shac.py:215-278; actor / twin critic of utils/policies/td_policies.py:82-252) -----------------
  * The networks are vf_mlp_desc layer tables like the PPO policy's (actor: two 4-wide heads mu / log_std over one extractor;
  * critic: features (+) action -> two Q trunks, the action columns entering through a frozen identity layer); the env step and

@@ -1,4 +1,4 @@
-"""VGPR / AGPR / spill / LDS figures of the kernels inside libvisfly_amd.so (the gfx950 code objects of the offload bundles, llvm-readelf
+"""VGPR / AGPR / spill / scratch / LDS figures of the kernels inside libvisfly_amd.so (the gfx950 code objects of the offload bundles, llvm-readelf
 --notes).  python tools/kernel_resources.py [regex] [shared object]"""
 import os, re, shutil, struct, subprocess, sys, tempfile
 
@@ -21,14 +21,14 @@ while pos != -1:
             for blk in out.split("- .agpr_count")[1:]:
                 g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
                 rows.append((g("vgpr_count"), int(re.search(r"^:\s+(\d+)", blk).group(1)), g("vgpr_spill_count"),
-                             g("group_segment_fixed_size"), re.search(r"\.name:\s+(\S+)", blk).group(1)))
+                             g("private_segment_fixed_size"), g("group_segment_fixed_size"), re.search(r"\.name:\s+(\S+)", blk).group(1)))
     pos = so.find(MAGIC, pos + len(MAGIC))
 shutil.rmtree(tmp)
 filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-names = [r[4] for r in rows]
+names = [r[5] for r in rows]
 if filt:
     names = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-print(f"{'vgpr':>5} {'agpr':>5} {'spill':>5} {'lds':>7}  kernel")
-for (v, a, sp, lds, _), d in sorted(zip(rows, names), reverse=True):
+print(f"{'vgpr':>5} {'agpr':>5} {'spill':>5} {'scratch':>7} {'lds':>7}  kernel")
+for (v, a, sp, scr, lds, _), d in sorted(zip(rows, names), reverse=True):
     if pat.search(d):
-        print(f"{v:5d} {a:5d} {sp:5d} {lds:7d}  {d[:160]}")
+        print(f"{v:5d} {a:5d} {sp:5d} {scr:7d} {lds:7d}  {d[:160]}")

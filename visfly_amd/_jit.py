@@ -19,7 +19,8 @@ columns, does not qualify).  Everything else keeps running on the block-tile ker
 Two more plugin kinds hold ONE instance each of a persistent launch for a generated class under one env kind / action type / integrator /
 motor-lag setting, built when a trainer first needs them: the roll-out plugin (PPO's collect_rollouts: ``ensure_rollout``,
 csrc/vf_ppo_rollout_kernel.hpp) and, r06, the BPTT plugin (both halves of a BPTT / SHAC horizon for an actor class: ``ensure_bptt``,
-csrc/vf_bptt_rollout_kernel.hpp + csrc/vf_bptt_reverse_kernel.hpp).
+csrc/vf_bptt_rollout_kernel.hpp + csrc/vf_bptt_reverse_kernel.hpp).  A third one holds the evaluation launch (deterministic episodes of
+``visfly_amd.evaluate``: ``ensure_eval``, csrc/vf_eval_rollout_kernel.hpp) of a class with a 4-wide mean head.
 """
 import hashlib
 import os
@@ -42,6 +43,7 @@ _ROLLOUT_HEADERS = ("vf_ppo_rollout_kernel.hpp", "vf_env_epilogue.hpp", "vf_env_
                     "vf_quad.hpp", "vf_handles.hpp")
 _BPTT_HEADERS = _ROLLOUT_HEADERS[1:] + ("vf_bptt_rollout_kernel.hpp", "vf_bptt_reverse_kernel.hpp", "vf_env_bwd_body.hpp", "vf_env_bwd_quad.hpp",
                                         "vf_dyn_quad.hpp")
+_EVAL_HEADERS = _ROLLOUT_HEADERS + ("vf_eval_rollout_kernel.hpp",)
 _loaded = {}
 # shapes compiled ahead of time by __graft_entry__.build() (name -> observation widths, extractor layers, pi, vf): the ones the parity
 # tests run (tests/test_chain_jit_gpu.py), so that a GPU box without a warm cache finds them in the snapshot
@@ -103,6 +105,9 @@ PREBUILD_BPTT = [("sac_hover", (0, 1, 0, True)), ("sac_nav_bptt", (1, 1, 0, True
 PREBUILD_ROLLOUT = [("verdict", (1, 1, 0, True)), ("one_layer_extractor", (0, 1, 1, False)), ("one_layer_extractor", (1, 1, 0, True)),
                     ("one_layer_extractor", (2, 1, 0, True)), ("one_layer_extractor", (3, 1, 0, True)),      # RacingEnv / RacingEnv2 (kernel-side kind 3)
                     ("gate_pi", (3, 1, 0, True))]                                                             # StateGateExtractor on RacingEnv2
+# ... and the evaluation plugins tests/test_evaluate_gpu.py runs: (shape name, (kernel-side env kind, VF_ACT_*, VF_INT_*, ctrl_delay)) -- the Tanh
+# default policy on NavigationEnv, StateGateExtractor's actor-critic on RacingEnv2, BPTT's Tanh SAC-style Actor on HoverEnv
+PREBUILD_EVAL = [("tanh_nav", (1, 1, 0, True)), ("gate_pi", (3, 1, 0, True)), ("sac_hover_tanh", (0, 1, 0, True))]
 
 
 def shape_of(obs_dims, extractor, pi, vf, head_dims=(4, 1), passthrough=(), acts=(1, 1)):
@@ -220,6 +225,15 @@ VF_CHAIN_PLUGIN_BPTT_DEFINE(Net, NetPi, {int(kind)}, {int(act)}, {int(integ)}, {
 """
 
 
+def eval_source(shape, cfg):
+    """the evaluation plugin of `shape` (heads (4, 1) or (4, 4)) under cfg = (KERNEL-side env kind, action type, integrator, ctrl_delay): ONE
+    class's instances (16 / 32 rows per wave) of the evaluation launch (csrc/vf_eval_rollout_kernel.hpp), compiled as part 8"""
+    kind, act, integ, delay = cfg
+    return source(shape) + f"""#include "vf_eval_rollout_kernel.hpp"
+VF_CHAIN_PLUGIN_EVAL_DEFINE(Net, {int(kind)}, {int(act)}, {int(integ)}, {"true" if delay else "false"}, "{name_of(shape)} evaluation kind {int(kind)} act {int(act)} int {int(integ)} delay {int(bool(delay))}")
+"""
+
+
 def _flags():
     extra = os.environ.get("VISFLY_AMD_JIT_FLAGS", "").split()       # e.g. -DVF_GEN_LIVE_TILES=0 (A/B builds; part of the cache key)
     return [f for f in HIPCC_FLAGS if f not in ("-shared", "-Wall")] + ["-ftemplate-depth=4096", "-Wno-unused-const-variable"] + extra + [
@@ -230,8 +244,15 @@ def _is_bptt(rollout):
     return rollout is not None and rollout[0] == "bptt"
 
 
+def _is_eval(rollout):
+    return rollout is not None and rollout[0] == "eval"
+
+
 def _source_of(shape, rollout):
-    """rollout: None (the chain plugin), (kind, act, integ, delay) (PPO's roll-out plugin) or ("bptt", kind, act, integ, delay)"""
+    """rollout: None (the chain plugin), (kind, act, integ, delay) (PPO's roll-out plugin), ("bptt", kind, act, integ, delay) or
+    ("eval", kind, act, integ, delay)"""
+    if _is_eval(rollout):
+        return eval_source(shape, rollout[1:])
     return source(shape) if rollout is None else bptt_source(shape, rollout[1:]) if _is_bptt(rollout) else rollout_source(shape, rollout)
 
 
@@ -239,7 +260,7 @@ def _key(shape, rollout=None):
     h = hashlib.sha256()
     h.update(_source_of(shape, rollout).encode())
     h.update(" ".join(_flags()[:-4]).encode())
-    for n in _HEADERS + (() if rollout is None else _BPTT_HEADERS if _is_bptt(rollout) else _ROLLOUT_HEADERS) + (os.path.join(INCLUDE, "visfly_amd.h"),):
+    for n in _HEADERS + (() if rollout is None else _BPTT_HEADERS if _is_bptt(rollout) else _EVAL_HEADERS if _is_eval(rollout) else _ROLLOUT_HEADERS) + (os.path.join(INCLUDE, "visfly_amd.h"),):
         with open(n if os.path.isabs(n) else os.path.join(CSRC, n), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -253,6 +274,8 @@ def _slug(shape, rollout=None):
         s += "_a%d%d" % _acts(shape)
     if _is_bptt(rollout):
         return s + "_bptt" + "".join(str(int(x)) for x in rollout[1:])
+    if _is_eval(rollout):
+        return s + "_eval" + "".join(str(int(x)) for x in rollout[1:])
     return s if rollout is None else s + "_roll" + "".join(str(int(x)) for x in rollout)
 
 
@@ -296,7 +319,7 @@ def build(shape, verbose=False, rollout=None):
             return obj
 
         with ThreadPoolExecutor(max_workers=4) as pool:
-            objs = list(pool.map(part, range(4) if rollout is None else [5, 6, 7] if _is_bptt(rollout) else [4]))
+            objs = list(pool.map(part, range(4) if rollout is None else [5, 6, 7] if _is_bptt(rollout) else [8] if _is_eval(rollout) else [4]))
         tmp = f"{out}.{os.getpid()}.tmp"       # private name, then rename: concurrent builders (ranks) never see a torn file
         try:
             r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp], capture_output=True, text=True)
@@ -362,6 +385,21 @@ def ensure_bptt(shape, cfg):
     return _loaded[key] is not None
 
 
+def ensure_eval(shape, cfg):
+    """the same for the evaluation plugin (the deterministic-episode launch of visfly_amd.evaluate) of a class with a 4-wide mean head under
+    cfg = (KERNEL-side env kind, action type, integrator, ctrl_delay)"""
+    if shape is None or is_builtin(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
+        return False
+    key = (shape, ("eval",) + tuple(int(x) for x in cfg))
+    if key not in _loaded:
+        from . import _lib
+        _loaded[key] = None
+        path = build(shape, rollout=key[1])
+        _lib.check(_lib.lib().vf_chain_plugin_load(path.encode()))
+        _loaded[key] = path
+    return _loaded[key] is not None
+
+
 def prebuild_shape(name):
     """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC / PREBUILD_CRITIC, or of PREBUILD_ACT (with its activations)"""
     if name in PREBUILD_ACT:
@@ -376,7 +414,8 @@ def prebuild(verbose=False):
     jobs = ([(shape_of(*v), None) for v in list(PREBUILD.values()) + list(PREBUILD_SAC.values()) + list(PREBUILD_CRITIC.values())] +
             [(sh, None) for sh in act] +
             [(shape_of(*PREBUILD[n]), cfg) for n, cfg in PREBUILD_ROLLOUT] + [(act[0], (1, 1, 0, True))] +       # + the Tanh policy's roll-out on NavigationEnv
-            [(prebuild_shape(n), ("bptt",) + cfg) for n, cfg in PREBUILD_BPTT])
+            [(prebuild_shape(n), ("bptt",) + cfg) for n, cfg in PREBUILD_BPTT] +
+            [(prebuild_shape(n), ("eval",) + cfg) for n, cfg in PREBUILD_EVAL])
     # every chain job runs four hipcc parts of fully unrolled kernels: bound the number in flight by the cores of the build box
     with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), (os.cpu_count() or 4) // 4))) as pool:
         paths = list(pool.map(lambda j: build(j[0], verbose, rollout=j[1]), jobs))

@@ -112,6 +112,12 @@ class PpoRolloutArgs(C.Structure):
                 [(n, C.c_void_p) for n in ("cursor", "idx_list", "rows0", "rows1", "stat", "out")])
 
 
+class EvalRolloutArgs(C.Structure):
+    """mirror of vf_eval_rollout_args"""
+    _fields_ = ([("T_max", C.c_int32), ("w1", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("obs_state", "obs_second", "obs_scratch", "ep_return", "ep_length", "ep_flags", "terminal_rows", "out")])
+
+
 class EnvRollout(C.Structure):
     """mirror of vf_env_rollout"""
     _fields_ = [("actions", C.c_void_p), ("action_stride", C.c_int64), ("out", EnvOut),
@@ -232,6 +238,9 @@ SIGNATURES = {
     "vf_bptt_rollout": (C.c_int, [_vp, C.POINTER(MlpDesc)] + [_vp] * 7 + [C.POINTER(EnvOut), _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp,
                                   C.c_float, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vf_ppo_rollout": (C.c_int, [_vp, C.POINTER(MlpDesc), _vp, _vp, C.POINTER(PpoRolloutArgs), _vp]),
+    "vf_eval_rollout": (C.c_int, [_vp, C.POINTER(MlpDesc), _vp, _vp, C.POINTER(EvalRolloutArgs), _vp]),
+    "vf_eval_latch": (C.c_int, [_vp] * 10 + [C.c_int32, C.c_int32, _vp]),
+    "vf_eval_action": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "vf_dyn_step_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vf_env_ring_phase": (C.c_int32, [_vp]),
     "vf_env_set_ring_phase": (C.c_int, [_vp, C.c_int32]),

@@ -76,7 +76,7 @@ LOG_STD_MAX, LOG_STD_MIN = 2.0, -10.0        # td_policies.py:31-32
 class BPTT:
     def __init__(self, env, horizon: int = 32, gamma: float = 0.99, learning_rate: float = 1e-3,
                  max_grad_norm: float = 0.5, weight_decay: float = 0.0, policy_kwargs: Optional[dict] = None,
-                 seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, policy=None):
+                 seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, policy=None, dump_step: float = 1e4):
         if policy is not None and not isinstance(policy, str):
             policy = getattr(policy, "__name__", str(policy))
         if policy is not None and policy not in REFERENCE_ACTOR_POLICIES:
@@ -85,6 +85,7 @@ class BPTT:
         self.reference_actor = policy is not None or getattr(self, "reference_actor", False)
         self._eps_override = None            # tests: the exploration noise of the next horizon(s), fed instead of drawn
         self.env, self.H, self.gamma = env, horizon, gamma
+        self.dump_step = dump_step          # learn(eval_env=...): timesteps between two evaluations (BPTT.py:137)
         self.lr, self.max_grad_norm, self.weight_decay, self.betas, self.adam_eps = learning_rate, max_grad_norm, weight_decay, betas, adam_eps
         self.device = env.device
         env.set_requires_grad(True, horizon=horizon)        # shac.py:124 sets env.requires_grad = True
@@ -468,10 +469,21 @@ class BPTT:
             return algo
         return checkpoint.load_into(cls(env, **checkpoint.ctor_kwargs_from_archive(path, kwargs)), path)
 
-    def learn(self, total_timesteps: int, log_interval: Optional[int] = None):
+    def learn(self, total_timesteps: int, log_interval: Optional[int] = None, eval_env=None):
+        """``eval_env``: every ``dump_step`` timesteps (BPTT.py:137,174) one deterministic episode per agent of that env
+        (visfly_amd.evaluate.evaluate_policy) -> logs["rollout/ep_rew_mean" | "rollout/ep_len_mean" | "rollout/success_rate"] by the
+        reference's 100-episode window of this call, logs["eval/..."] over the episodes of the last evaluation (all ranks).  The
+        evaluation draws no noise and leaves the training env, its tape and every generator alone; without ``eval_env`` nothing changes"""
         t0, start, it = time.time(), self.num_timesteps, 0
+        sched = None
+        if eval_env is not None:
+            from .evaluate import EvalSchedule
+            sched = self._eval_schedule = EvalSchedule(self, eval_env, self.dump_step)
         while self.num_timesteps - start < total_timesteps:
+            before = self.num_timesteps - start
             loss = self._update()
+            if sched is not None:
+                sched.after_update(before, self.num_timesteps - start, self.logs)
             it += 1
             if log_interval and it % log_interval == 0:
                 self.logs["train/actor_loss"] = float(loss)

@@ -263,7 +263,8 @@ int plugin_bptt_reverse(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg
     extern "C" const vf::ChainPlugin* vf_chain_plugin()                                                                                         \
     {                                                                                                                                           \
         static const vf::ChainPlugin p{vf::kChainPluginAbi, NAME, nullptr, nullptr, nullptr, nullptr, 0u, nullptr,                              \
-                                       vf::kBpttRollPluginAbi, vf::kBpttRevPluginAbi, vf_plugin_bptt_rollout, vf_plugin_bptt_reverse};          \
+                                       vf::kBpttRollPluginAbi, vf::kBpttRevPluginAbi, vf_plugin_bptt_rollout, vf_plugin_bptt_reverse,           \
+                                       0u, nullptr};                                                                                            \
         return &p;                                                                                                                              \
     }
 #endif

@@ -5,6 +5,7 @@
 #include "vf_ppo_rollout_kernel.hpp"
 #include "vf_bptt_rollout_kernel.hpp"
 #include "vf_bptt_reverse_kernel.hpp"
+#include "vf_eval_rollout_kernel.hpp"
 
 #include <dlfcn.h>
 
@@ -15,16 +16,17 @@
 
 namespace vf {
 
-// PPO: the actor-critic classes (fused PPO step, PPO roll-out); BPTT: the actor classes (a horizon's two persistent launches)
+// PPO: the actor-critic classes (fused PPO step, PPO roll-out); BPTT: the actor classes (a horizon's two persistent launches, and the
+// evaluation launch: every class with a 4-wide mean head)
 template <class Net, class NetPi, bool PPO, bool BPTT>
 constexpr ChainPlugin builtin_entry(const char* name)
 {
     using B = Builtin<Net, NetPi>;
     ChainPlugin e{kChainPluginAbi, name, B::forward, B::backward, nullptr, nullptr, kRolloutPluginAbi, nullptr, kBpttRollPluginAbi,
-                  kBpttRevPluginAbi, nullptr, nullptr};
+                  kBpttRevPluginAbi, nullptr, nullptr, kEvalPluginAbi, nullptr};
     if constexpr (PPO) e.ppo_update = B::ppo_update, e.ppo_rollout = B::ppo_rollout;
     if constexpr (Net::PASS != 0) e.twin_q_update = B::twin_q_update;
-    if constexpr (BPTT) e.bptt_rollout = B::bptt_rollout, e.bptt_reverse = B::bptt_reverse;
+    if constexpr (BPTT) e.bptt_rollout = B::bptt_rollout, e.bptt_reverse = B::bptt_reverse, e.eval_rollout = B::eval_rollout;
     return e;
 }
 
@@ -87,15 +89,18 @@ extern "C" int vf_chain_plugin_load(const char* path)
     typedef const ChainPlugin* (*entry_t)();
     entry_t entry = reinterpret_cast<entry_t>(dlsym(h, "vf_chain_plugin"));
     const ChainPlugin* p = entry ? entry() : nullptr;
-    if (!p || p->abi != kChainPluginAbi || !((p->forward && p->backward && p->ppo_update) || p->ppo_rollout || (p->bptt_rollout && p->bptt_reverse))) {
+    if (!p || p->abi != kChainPluginAbi || !((p->forward && p->backward && p->ppo_update) || p->ppo_rollout || (p->bptt_rollout && p->bptt_reverse) ||
+                                              p->eval_rollout)) {
+        const unsigned abi = p ? p->abi : 0u;      // (p points into the object: read before it is unmapped)
         dlclose(h);
         return fail(VF_EINVAL, "vf_chain_plugin_load: %s is not a chain plugin of this library build (abi %08x, expected %08x)", path,
-                    p ? p->abi : 0u, kChainPluginAbi);
+                    abi, kChainPluginAbi);
     }
     ChainPlugin q = *p;
     if (q.rollout_abi != kRolloutPluginAbi) q.ppo_rollout = nullptr;
     if (q.bptt_roll_abi != kBpttRollPluginAbi) q.bptt_rollout = nullptr;
     if (q.bptt_rev_abi != kBpttRevPluginAbi) q.bptt_reverse = nullptr;
+    if (q.eval_abi != kEvalPluginAbi) q.eval_rollout = nullptr;
     loaded().push_back(Loaded{path, h, q});
     return VF_OK;
 }

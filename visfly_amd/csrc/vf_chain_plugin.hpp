@@ -5,7 +5,7 @@
 //   * the chain plugins: shared objects, compiled on first use for one network shape (visfly_amd/_jit.py), that hold the kernels of that
 //     shape (vf_mlp_chain_gen.hpp) and the member functions below; loaded with vf_chain_plugin_load (include/visfly_amd.h).
 // Every chain entry point (mlp_forward_chain_try, mlp_backward_chain_try, ppo_update_chain_try, twin_q_update_chain_try, vf_ppo_rollout,
-// vf_bptt_rollout, vf_bptt_reverse) validates its arguments, then asks the table once through chain_serve.  Return values of a member:
+// vf_bptt_rollout, vf_bptt_reverse, vf_eval_rollout) validates its arguments, then asks the table once through chain_serve.  Return values of a member:
 // 1 launched (or, for a query, "would launch"), 0 not this class / configuration, < 0 error (a plugin: -1000 - hipError_t).
 #pragma once
 #include "vf_mlp_chain_kernels.hpp"
@@ -16,8 +16,9 @@
 namespace vf {
 
 // layout stamp: both sides are compiled from the same headers; a plugin built against other struct layouts is refused
-// (0005: the env constant block the persistent launches are handed is a vf_env_dev -- vf_env_cfg + the first global agent id)
-constexpr unsigned kChainPluginAbi = 0x56460005u ^ (unsigned)(sizeof(vf_mlp_desc) * 31u + sizeof(vf_mlp_bwd_desc) * 17u + sizeof(ChainArgs) * 7u +
+// (0005: the env constant block the persistent launches are handed is a vf_env_dev -- vf_env_cfg + the first global agent id;
+// 0006: ChainPlugin ends in eval_abi / eval_rollout)
+constexpr unsigned kChainPluginAbi = 0x56460006u ^ (unsigned)(sizeof(vf_mlp_desc) * 31u + sizeof(vf_mlp_bwd_desc) * 17u + sizeof(ChainArgs) * 7u +
                                                             sizeof(BwdArgsChain) * 5u + sizeof(PpoRowArgs) * 3u + sizeof(ReparamFwd) + sizeof(ReparamBwd));
 
 // out1 == null: the policy-only class (no value trunk).  M_choice > 0: the rows-per-wave choice is made for M_choice rows
@@ -36,6 +37,10 @@ using TwinQUpdateFn = int(const ChainArgs* g, const BwdArgsChain* gb, const floa
 using PpoRolloutFn = int(const vf_mlp_desc* d, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
                          const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
 using BpttRolloutFn = int(const vf_mlp_desc* d, const float* params, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn,
+                          const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
+// the evaluation launch (vf_eval_rollout.hip): env_args / roll_args are vf::EnvArgs / vf::EvalRollArgs (vf_eval_rollout_kernel.hpp); params: the
+// rows-per-wave choice reads their alignment (chain16_ok)
+using EvalRolloutFn = int(const vf_mlp_desc* d, const float* params, int env_kind, const vf_dyn_cfg* c, int has_target, const vf_dyn_cfg* d_dyn,
                           const vf_env_cfg* d_env, const void* env_args, const ChainArgs* gc, const void* roll_args, int N, hipStream_t st);
 using BpttReverseFn = int(const vf_mlp_bwd_desc* d, int env_kind, const vf_dyn_cfg* c, const vf_dyn_cfg* d_dyn, const vf_env_cfg* d_env,
                           const BwdArgsChain* gb, const void* rev_args, int N, hipStream_t st);
@@ -60,6 +65,10 @@ struct ChainPlugin {
     unsigned bptt_roll_abi, bptt_rev_abi;
     BpttRolloutFn* bptt_rollout;
     BpttReverseFn* bptt_reverse;
+    // an EVALUATION plugin (per shape AND env kind / action type / integrator / ctrl_delay, like the roll-out plugin): the deterministic
+    // episode launch k_eval_rollout for a class with a 4-wide mean head; eval_abi stamps the layout of its arguments
+    unsigned eval_abi;
+    EvalRolloutFn* eval_rollout;
 };
 
 }  // namespace vf
@@ -70,7 +79,8 @@ namespace vf {
 
 // the members of built-in class Net (NetPi: its policy-only form, the class a BPTT horizon steps), each defined and instantiated in the
 // translation unit that holds its kernel instances: forward vf_mlp_chain.hip, backward vf_mlp_chain_reverse.hip, ppo_update /
-// twin_q_update vf_mlp_chain_split.hip, ppo_rollout vf_ppo_rollout.hip, bptt_rollout vf_bptt_rollout.hip, bptt_reverse vf_bptt_reverse.hip
+// twin_q_update vf_mlp_chain_split.hip, ppo_rollout vf_ppo_rollout.hip, bptt_rollout vf_bptt_rollout.hip, bptt_reverse vf_bptt_reverse.hip,
+// eval_rollout vf_eval_rollout.hip
 template <class Net, class NetPi = Net>
 struct Builtin {
     static ChainForwardFn forward;
@@ -80,6 +90,7 @@ struct Builtin {
     static PpoRolloutFn ppo_rollout;
     static BpttRolloutFn bptt_rollout;
     static BpttReverseFn bptt_reverse;
+    static EvalRolloutFn eval_rollout;
 };
 
 // the table: the built-in classes (vf_chain_plugin.hip), then the loaded plugins (registry, vf_chain_plugin.hip)
@@ -257,14 +268,14 @@ const vf::ChainPlugin* vf_chain_plugin();
 #define VF_CHAIN_PLUGIN_DEFINE(Net, NetPi, NAME)
 #elif VF_CHAIN_PLUGIN_PART >= 5
 // the BPTT plugin: parts 5 (k_bptt_rollout), 6 (k_bptt_reverse), 7 (the table): vf_bptt_rollout_kernel.hpp / vf_bptt_reverse_kernel.hpp
-// define VF_CHAIN_PLUGIN_BPTT_DEFINE
+// define VF_CHAIN_PLUGIN_BPTT_DEFINE; part 8: the evaluation plugin (vf_eval_rollout_kernel.hpp defines VF_CHAIN_PLUGIN_EVAL_DEFINE)
 #define VF_CHAIN_PLUGIN_DEFINE(Net, NetPi, NAME)
 #else
 #define VF_CHAIN_PLUGIN_DEFINE(Net, NetPi, NAME)                                                                                             \
     extern "C" const vf::ChainPlugin* vf_chain_plugin()                                                                                      \
     {                                                                                                                                        \
         static const vf::ChainPlugin p{vf::kChainPluginAbi, NAME, vf_plugin_forward, vf_plugin_backward, vf_plugin_ppo_update,               \
-                                       Net::PASS ? vf_plugin_twin_q_update : nullptr, 0u, nullptr, 0u, 0u, nullptr, nullptr};                \
+                                       Net::PASS ? vf_plugin_twin_q_update : nullptr, 0u, nullptr, 0u, 0u, nullptr, nullptr, 0u, nullptr};                \
         return &p;                                                                                                                           \
     }
 #endif

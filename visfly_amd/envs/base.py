@@ -965,6 +965,73 @@ class DroneGymEnvsBase:
     def _after_persistent_launch(self):
         """host-side caches of per-step state that a persistent launch stepped past (overridden where an env keeps any)"""
 
+    def _launch_scratch(self):
+        """reward / done / observation scratch and the vf_env_out of the persistent PPO roll-out and evaluation launches"""
+        sc = getattr(self, "_collect_scratch", None)
+        if sc is None:
+            N, W, dev = self.num_agent, self._OBS_W, self.device
+            sc = self._collect_scratch = {"reward": th.empty(N, dtype=th.float32, device=dev),
+                                          "done": th.empty(N, dtype=th.bool, device=dev),
+                                          "state": th.empty((N, W), dtype=th.float32, device=dev)}
+            sc["out"] = self._out(sc["state"], sc["reward"], sc["done"])
+            if W != 13:         # the launch's terminal rows are W wide as well: a buffer of their own
+                sc["terminal"] = th.zeros((N, W), dtype=th.float32, device=dev)
+                sc["out"].terminal_obs = _lib.ptr(sc["terminal"])
+        return sc
+
+    def evaluate_policy_launch(self, policy, obs_keys, rows, ep_return, ep_length, ep_flags, terminal_rows=None):
+        """one deterministic episode per agent from the current (freshly reset) state -- a = tanh(mean(obs)) -> step(is_test=True)
+        until every agent is done, max_episode_steps steps at the latest -- in ONE persistent launch (vf_eval_rollout).  rows: the
+        policy's observation rows of the current state (ppo.policy_rows); ep_return (N,) f32 / ep_length (N,) i32 / ep_flags (N,) u8 /
+        terminal_rows (N, W) or None take every agent's episode as reported at its FIRST done step.  -> True, or False when the launch
+        does not serve this env / network / dynamics configuration: collect_policy's conditions, except that a tape may exist (nothing is
+        recorded).  Afterwards the env needs a reset() (waves leave the launch once their agents are done)."""
+        W = self._OBS_W
+        if (self.spawn_mode != "device" or self._imu_noise is not None or self._half_step
+                or self.envs.dynamics._wind_fn is not None or (getattr(self, "_HOST_OBS", False) and W == 13) or not self.tensor_output
+                or getattr(self, "obs_gate_exact", False)
+                or (W == 13 and self._terminal_state_rows() is not self._terminal_obs)
+                or not self._persistent_keys_ok(obs_keys) or policy._plan is None or not policy.fused
+                or policy.obs_dims.get("state") != W):
+            return False
+        assert self._is_initial, "You should call reset() before step()"
+        N = self.num_agent
+        key = (N, 0, False)
+        d = policy._descs.get(key)
+        if d is None:
+            d = policy._descs[key] = policy._fused_desc(policy._buffers(N, 0), False)
+        policy._pack()
+        sc = self._launch_scratch()
+        o1 = rows["target"] if "target" in obs_keys else rows["gate"] if "gate" in obs_keys else None
+        a = _lib.EvalRolloutArgs()
+        a.T_max, a.w1 = self.max_episode_steps, 0 if o1 is None else o1.shape[-1]
+        a.obs_state, a.obs_second, a.obs_scratch = _lib.ptr(rows["state"]), _lib.ptr(o1), _lib.ptr(sc["state"])
+        a.ep_return, a.ep_length, a.ep_flags = _lib.ptr(ep_return), ep_length.data_ptr(), ep_flags.data_ptr()
+        a.terminal_rows = _lib.ptr(terminal_rows)
+        a.out = C.addressof(sc["out"])
+        if getattr(policy, "chain_jit", False):
+            # a generated chain class: its evaluation launch is one more plugin, per env kind / action type / integrator / motor lag
+            try:
+                from .. import _jit
+                c = self.envs.dynamics.constants
+                kind = 3 if W == 16 else self.KIND          # kernel-side kind: VF_ENV_RACING2 forms RacingEnv2's 16 columns itself
+                _jit.ensure_eval(policy.chain_shape, (kind, int(c["action_type"]), int(c["integrator"]), bool(c["ctrl_delay"])))
+            except Exception as e:          # no hipcc, ...: launch by launch, with the warning below
+                import warnings
+                warnings.warn(f"visfly_amd: no evaluation plugin for this network ({e})")
+        with th.cuda.device(self.device):
+            rc = _lib.lib().vf_eval_rollout(self._h, C.byref(d), _lib.ptr(policy.flat), _lib.ptr(policy._packed), C.byref(a), self._stream())
+        if rc == _lib.EUNSUPPORTED:
+            _lib.warn_unsupported("vf_eval_rollout")
+            return False
+        if rc:
+            _lib.check(rc)
+        self._qcache = self._imu_cache = self._ext_col = None
+        self._reward, self._done = sc["reward"], sc["done"]
+        self._after_persistent_launch()
+        self._is_initial = False
+        return True
+
     def collect_policy(self, policy, obs_keys, buf, boot, noise_key, sample_step, last_starts):
         """T = buf.actions.shape[0] rounds of PPO's collect_rollouts loop -- policy.forward (both heads), squashed-Gaussian
         sample + log-prob (Philox counters sample_step + 1 ..), env.step, RolloutBuffer rows, TimeLimit list / episode
@@ -987,15 +1054,7 @@ class DroneGymEnvsBase:
         if d is None:
             d = policy._descs[key] = policy._fused_desc(b0, False)
         policy._pack()
-        sc = getattr(self, "_collect_scratch", None)
-        if sc is None:
-            sc = self._collect_scratch = {"reward": th.empty(N, dtype=th.float32, device=dev),
-                                          "done": th.empty(N, dtype=th.bool, device=dev),
-                                          "state": th.empty((N, W), dtype=th.float32, device=dev)}
-            sc["out"] = self._out(sc["state"], sc["reward"], sc["done"])
-            if W != 13:         # the launch's terminal rows are W wide as well: a buffer of their own
-                sc["terminal"] = th.zeros((N, W), dtype=th.float32, device=dev)
-                sc["out"].terminal_obs = _lib.ptr(sc["terminal"])
+        sc = self._launch_scratch()
         final = th.empty((N, W), dtype=th.float32, device=dev)
         # the second observation: the constant "target" rows, or the "gate" column (row 0 the caller's, the later rows the launch's)
         o1 = buf.obs["target"] if "target" in obs_keys else buf.obs["gate"] if "gate" in obs_keys else None

@@ -1522,16 +1522,26 @@ class PPO:
         _lib.check(_lib.lib().vf_gather_rows(C.byref(gf), perm.data_ptr(), perm.numel(), self._stream()))
         return dict(dst)
 
-    def learn(self, total_timesteps: int, log_interval: Optional[int] = None):
-        """PPO.learn (PPO.py:116-175): alternate rollout collection and training"""
+    def learn(self, total_timesteps: int, log_interval: Optional[int] = None, eval_env=None, eval_freq: Optional[int] = None):
+        """PPO.learn (PPO.py:116-175): alternate rollout collection and training.  ``eval_env``: after an iteration, once ``eval_freq``
+        timesteps have passed since the last evaluation (None: after every iteration), one deterministic episode per agent of that env
+        (visfly_amd.evaluate.evaluate_policy) -> logs["rollout/ep_rew_mean" | "rollout/ep_len_mean" | "rollout/success_rate"] by the
+        reference's 100-episode window of this call (in place of the training episodes' means), logs["eval/..."] over the last
+        evaluation's episodes.  Draws no noise; without ``eval_env`` nothing changes"""
         t0 = time.time()
         start = self.num_timesteps
         it = 0
+        sched = None
+        if eval_env is not None:
+            from .evaluate import EvalSchedule
+            sched = self._eval_schedule = EvalSchedule(self, eval_env, 0 if eval_freq is None else eval_freq)
         while self.num_timesteps - start < total_timesteps:
             self.collect_rollouts()
             # SB3 _update_current_progress_remaining (PPO.py:150-152): after the rollout, before train()
             self._current_progress_remaining = 1.0 - float(self.num_timesteps - start) / float(total_timesteps)
             self.train()
+            if sched is not None:          # (measured from the end of the iteration: an evaluation every eval_freq timesteps)
+                sched.after_update(self.num_timesteps - start, self.num_timesteps - start, self.logs)
             it += 1
             if log_interval and it % log_interval == 0:
                 th.cuda.synchronize(self.device)

@@ -61,7 +61,7 @@ class SHAC(BPTT):
         self.fused_critic = True       # a critic update's per-row part as one launch (vf_twin_q_update); False: the three-launch step (tests)
         kw.pop("policy", None)
         super().__init__(env, horizon=horizon, gamma=gamma, learning_rate=learning_rate, max_grad_norm=max_grad_norm,
-                         policy_kwargs=policy_kwargs, seed=seed, **kw)
+                         policy_kwargs=policy_kwargs, seed=seed, dump_step=dump_step, **kw)
         pol, dev = self.policy, self.device
         obs_dims = {k: pol.obs_dims[k] for k in self._ext_keys}
         mk = lambda s: MlpPolicy({**obs_dims, "action": 4}, self._extractor, self._critic_arch, self._critic_arch, dev, seed=s,
@@ -251,8 +251,8 @@ class SHAC(BPTT):
             self.logs["train/actor_loss"], self.logs["train/critic_loss"] = float(a), float(c)
         return self.logs
 
-    def learn(self, total_timesteps: int, log_interval: Optional[int] = None):
-        out = super().learn(total_timesteps, log_interval)
+    def learn(self, total_timesteps: int, log_interval: Optional[int] = None, eval_env=None):
+        out = super().learn(total_timesteps, log_interval, eval_env=eval_env)
         self.flush_logs()
         return out
 
