@@ -104,10 +104,13 @@ PREBUILD_BPTT = [("sac_hover", (0, 1, 0, True)), ("sac_nav_bptt", (1, 1, 0, True
                  ("gate_sac", (3, 0, 0, True)), ("gate_pi", (3, 0, 0, True)), ("gate_sac", (2, 0, 0, True))]
 PREBUILD_ROLLOUT = [("verdict", (1, 1, 0, True)), ("one_layer_extractor", (0, 1, 1, False)), ("one_layer_extractor", (1, 1, 0, True)),
                     ("one_layer_extractor", (2, 1, 0, True)), ("one_layer_extractor", (3, 1, 0, True)),      # RacingEnv / RacingEnv2 (kernel-side kind 3)
-                    ("gate_pi", (3, 1, 0, True))]                                                             # StateGateExtractor on RacingEnv2
+                    ("gate_pi", (3, 1, 0, True)),                                                             # StateGateExtractor on RacingEnv2
+                    # the geometric controller's action types (tests/test_geometric_rollout_gpu.py): velocity on HoverEnv, position on NavigationEnv2
+                    ("one_layer_extractor", (0, 2, 0, True)), ("one_layer_extractor", (1, 3, 0, True))]
 # ... and the evaluation plugins tests/test_evaluate_gpu.py runs: (shape name, (kernel-side env kind, VF_ACT_*, VF_INT_*, ctrl_delay)) -- the Tanh
 # default policy on NavigationEnv, StateGateExtractor's actor-critic on RacingEnv2, BPTT's Tanh SAC-style Actor on HoverEnv
-PREBUILD_EVAL = [("tanh_nav", (1, 1, 0, True)), ("gate_pi", (3, 1, 0, True)), ("sac_hover_tanh", (0, 1, 0, True))]
+PREBUILD_EVAL = [("tanh_nav", (1, 1, 0, True)), ("gate_pi", (3, 1, 0, True)), ("sac_hover_tanh", (0, 1, 0, True)),
+                 ("tanh_nav", (1, 3, 0, True))]                                                               # ... with position actions
 
 
 def shape_of(obs_dims, extractor, pi, vf, head_dims=(4, 1), passthrough=(), acts=(1, 1)):

@@ -73,6 +73,23 @@ REFERENCE_ACTOR_POLICIES = ("MultiInputPolicy", "MTDPolicy", "CnnPolicy", "MlpPo
 LOG_STD_MAX, LOG_STD_MIN = 2.0, -10.0        # td_policies.py:31-32
 
 
+def _require_differentiable_actions(env, trainer):
+    """the adjoint (vf_env_step_bwd, vf_bptt_rollout / vf_bptt_reverse) covers the thrust and bodyrate action types.  The geometric
+    controller of velocity / position has no reference gradient to pin: the reference's own autograd raises on it (the per-agent loop of
+    envs/base/dynamics.py:446-450,481-488 writes in place into tensors the graph needs, and builds pose_err / the yaw-rate vector with
+    th.as_tensor / th.tensor, which detach them).  PPO and evaluate_policy run these two action types."""
+    from .constants import ACTION_TYPES
+    dyn = getattr(getattr(env, "envs", None), "dynamics", None)
+    act = None if dyn is None else int(dyn.constants["action_type"])
+    for name in ("velocity", "position"):
+        if act == ACTION_TYPES[name]:
+            raise NotImplementedError(
+                f"{trainer} over action_type=\"{name}\": the reference's autograd raises for the geometric controller of the velocity / "
+                "position action types (\"one of the variables needed for gradient computation has been modified by an inplace "
+                "operation\"; parts of its graph are detached as well), so there is no gradient to reproduce.  The env-step adjoint covers "
+                "\"thrust\" and \"bodyrate\"; train these action types with PPO")
+
+
 class BPTT:
     def __init__(self, env, horizon: int = 32, gamma: float = 0.99, learning_rate: float = 1e-3,
                  max_grad_norm: float = 0.5, weight_decay: float = 0.0, policy_kwargs: Optional[dict] = None,
@@ -81,6 +98,7 @@ class BPTT:
             policy = getattr(policy, "__name__", str(policy))
         if policy is not None and policy not in REFERENCE_ACTOR_POLICIES:
             raise NotImplementedError(f"policy {policy}: one of {REFERENCE_ACTOR_POLICIES} (vector observations) or None")
+        _require_differentiable_actions(env, type(self).__name__)
         # True: the reference's own actor (two trunks, mu / clamped state-dependent log_std heads); SHAC always uses it
         self.reference_actor = policy is not None or getattr(self, "reference_actor", False)
         self._eps_override = None            # tests: the exploration noise of the next horizon(s), fed instead of drawn

@@ -170,9 +170,11 @@ constexpr bool bptt_instance(int NB, int kind, bool delay)
 }
 
 // the persistent launches' kernels are templates over the run-time configuration: f(kind, act, integ, delay) is called with the kernel-side
-// env kind, action type, integrator and motor-lag form as std::integral_constant values.  0: an env kind / action type without instances
-// (the geometric controllers); any integrator but RK4 is Euler's
-template <class F>
+// env kind, action type, integrator and motor-lag form as std::integral_constant values.  0: an env kind / action type without instances;
+// any integrator but RK4 is Euler's.  GEOMETRIC: the caller also has instances for the velocity / position action types (the geometric
+// SO(3) controller: PPO's roll-out and the evaluation launch).  The BPTT launches do not ask: the reference's autograd raises for these
+// two action types, so there is no gradient to mirror, and their dispatchers instantiate nothing for them
+template <bool GEOMETRIC = false, class F>
 int with_env_config(int kind, const vf_dyn_cfg& c, F&& f)
 {
     auto delay = [&](auto k, auto a, auto i) -> int {
@@ -185,6 +187,10 @@ int with_env_config(int kind, const vf_dyn_cfg& c, F&& f)
     auto act = [&](auto k) -> int {
         if (c.action_type == VF_ACT_THRUST) return integ(k, std::integral_constant<int, VF_ACT_THRUST>{});
         if (c.action_type == VF_ACT_BODYRATE) return integ(k, std::integral_constant<int, VF_ACT_BODYRATE>{});
+        if constexpr (GEOMETRIC) {
+            if (c.action_type == VF_ACT_VELOCITY) return integ(k, std::integral_constant<int, VF_ACT_VELOCITY>{});
+            if (c.action_type == VF_ACT_POSITION) return integ(k, std::integral_constant<int, VF_ACT_POSITION>{});
+        }
         return 0;
     };
     switch (kind) {

@@ -19,9 +19,9 @@
 
 namespace vf {
 
-// the actor-critic classes (PPO; the one-head BPTT actor); the SAC-style Actor's instances: vf_eval_rollout_sac.hip
+// the one-observation actor-critic class (PPO; the one-head BPTT actor); the state + target class: vf_eval_rollout_nav.hip; the SAC-style
+// Actor's instances: vf_eval_rollout_sac.hip
 template EvalRolloutFn Builtin<NetHover, NetHoverPi>::eval_rollout;
-template EvalRolloutFn Builtin<NetNav, NetNavPi>::eval_rollout;
 
 __global__ __launch_bounds__(kBlock) void k_eval_action(const float* __restrict__ mean, float* __restrict__ action, int n)
 {
@@ -80,8 +80,8 @@ extern "C" int vf_eval_rollout(vf_env* h, const vf_mlp_desc* desc, const float* 
     if (rc < 0) return rc;
     if (rc == 0)
         return vf::fail(VF_EUNSUPPORTED, "vf_eval_rollout: no persistent evaluation for this network class / env kind / dynamics configuration "
-                                         "(built in: the [128, 64] x [64, 64] actor-critic and SAC-style Actor, Hover / Navigation / Racing, "
-                                         "thrust / bodyrate, Euler / RK4; generated classes: through their evaluation plugin)");
+                                         "(built in: the [128, 64] x [64, 64] actor-critic -- thrust / bodyrate / velocity / position -- and SAC-style Actor "
+                                         "-- thrust / bodyrate --, Hover / Navigation / Racing, Euler / RK4; generated classes: through their evaluation plugin)");
     h->dyn.tick += T;
     h->stale_all = 1;
     return VF_OK;

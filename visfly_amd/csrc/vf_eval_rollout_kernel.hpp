@@ -130,7 +130,9 @@ int Builtin<Net, NetPi>::eval_rollout(const vf_mlp_desc* d, const float* params,
     const EnvArgs& ge = *static_cast<const EnvArgs*>(env_args);
     const EvalRollArgs& r = *static_cast<const EvalRollArgs*>(roll_args);
     if (Net::NB == 2 && (env_kind == VF_ENV_RACING || env_kind == VF_ENV_RACING2) && (!r.gate0 || d->in_dim[1] != 1)) return 0;
-    return with_env_config(env_kind, *c, [&](auto kind, auto act, auto integ, auto delay) -> int {
+    // the actor-critic classes (what PPO trains) over all four action types; the SAC-style Actor is BPTT's / SHAC's, which have no
+    // velocity / position horizon (vf_env_device.hpp: with_env_config)
+    return with_env_config<Net::HV == 1>(env_kind, *c, [&](auto kind, auto act, auto integ, auto delay) -> int {
         constexpr int K = decltype(kind)::value, A = decltype(act)::value, I = decltype(integ)::value;
         constexpr bool D = decltype(delay)::value;
         if constexpr (eval_instance(Net::NB, K, D)) {
