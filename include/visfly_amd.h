@@ -591,7 +591,14 @@ int64_t vf_mlp_packed_floats(const vf_mlp_desc* desc);
  * input, vf_mlp_desc.identity_mask) has generated classes too, served by vf_mlp_forward / vf_mlp_backward_data / vf_twin_q_update; and a
  * generated ACTOR class gets one more plugin per env kind / action type / integrator / motor lag that holds its instances of the two
  * persistent launches of a horizon: vf_bptt_rollout / vf_bptt_reverse then serve its layer table (16 agents per wave with the sub-step
- * tape: N <= 16 384 per launch), as vf_ppo_rollout does from the roll-out plugin. */
+ * tape: N <= 16 384 per launch), as vf_ppo_rollout does from the roll-out plugin.
+ * Plugin kinds, all behind the same three entry points below: the chain plugin of a shape (forward / backward / ppo_update / twin_q_update
+ * members), its roll-out, BPTT and evaluation plugins (one persistent launch each), and the SEPARATE-EXTRACTOR chain plugin
+ * (csrc/vf_mlp_chain_sep.hpp; no new entry point, ABI unchanged): an actor-critic whose policy and value sides have extractors of their
+ * own -- layer table [pi extractor][vf extractor][pi trunk, mean][vf trunk, value] with one feature buffer per side -- is two independent
+ * single-trunk chains; its plugin's forward and ppo_update members run them as the two waves of one workgroup per 32 rows, nothing
+ * exchanged.  Its reverse chain alone and the persistent launches are not instantiated: those calls run on the block-tile kernels /
+ * launch by launch. */
 int vf_chain_plugin_load(const char* path);
 int vf_chain_plugin_count(void);
 const char* vf_chain_plugin_name(int32_t i);

@@ -16,6 +16,12 @@ one of the four: sum of the branches' last widths + action columns <= 128; the r
 columns, does not qualify).  Everything else keeps running on the block-tile kernels (MlpPolicy warns once).
 ``VISFLY_AMD_JIT=0`` switches the compilation off.
 
+An actor-critic with SEPARATE pi / vf feature extractors (MlpPolicy ``vf_extractor``: the reference's share_features_extractor=False and
+its pi_features_extractor_class / vf_features_extractor_class) qualifies when each side alone does and the two sides read at most two
+observation keys in all.  Its translation unit names two single-trunk Specs -- A: pi-side extractor + pi trunk + the 4-wide mean head, B:
+vf-side extractor + vf trunk + the 1-wide value head -- and its forward / fused PPO step give each of two waves per 32 rows one of them
+(csrc/vf_mlp_chain_sep.hpp).  Own slug, name and cache file; never a built-in class; no roll-out, BPTT or evaluation plugin.
+
 Two more plugin kinds hold ONE instance each of a persistent launch for a generated class under one env kind / action type / integrator /
 motor-lag setting, built when a trainer first needs them: the roll-out plugin (PPO's collect_rollouts: ``ensure_rollout``,
 csrc/vf_ppo_rollout_kernel.hpp) and, r06, the BPTT plugin (both halves of a BPTT / SHAC horizon for an actor class: ``ensure_bptt``,
@@ -92,6 +98,21 @@ PREBUILD_SAC = {
     "sac_nav_bptt": ({"state": 13, "target": 3}, {"state": [64, 64], "target": [32]}, [64], [64], (4, 4)),      # ... over StateTargetExtractor, pi=[64]
     "gate_sac": ({"state": 16, "gate": 1}, {"state": [64, 32], "gate": [32]}, [32], [32], (4, 4)),              # ... over StateGateExtractor (BPTT's Actor, SHAC)
 }
+# separate pi / vf feature extractors (MlpPolicy ``vf_extractor``; tests/test_separate_extractors_gpu.py): (observation widths, pi-side
+# extractor, pi, vf, vf-side extractor, (trunk, pi extractor, vf extractor) activations)
+PREBUILD_SEP = {
+    "sep_sym": ({"state": 13}, {"state": [64, 32]}, [32], [32], {"state": [64, 32]}, (1, 1, 1)),
+    # an asymmetric critic: the actor reads "state", the critic "state" and "target"; different depths and widths per role
+    "sep_asym": ({"state": 13, "target": 3}, {"state": [64]}, [32, 32], [64], {"state": [64, 32], "target": [32]}, (1, 1, 1)),
+    "sep_asym_tanh": ({"state": 13, "target": 3}, {"state": [64]}, [32, 32], [64], {"state": [64, 32], "target": [32]}, (2, 1, 1)),
+    # the reference's two forms on NavigationEnv with its default Tanh trunks: StateTargetExtractor twice, and StateExtractor /
+    # StateTargetExtractor (what the trainer tests and the fixture run)
+    "sep_nav_tanh": ({"state": 13, "target": 3}, {"state": [64, 32], "target": [32]}, [32], [32], {"state": [64, 32], "target": [32]}, (2, 1, 1)),
+    # the YAMLs' sizes on both sides (tools/bench_separate_extractors.py): 17 forward tiles per role -- the fused step keeps its ReLU masks
+    # as bits (csrc/vf_mlp_chain_sep.hpp: kSepLiveTiles)
+    "sep_default": ({"state": 13, "target": 3}, {"state": [128, 64], "target": [128, 64]}, [64, 64], [64, 64],
+                    {"state": [128, 64], "target": [128, 64]}, (1, 1, 1)),
+}
 # ... and their roll-out plugins for the configurations tests/test_ppo_gpu.py runs: (shape name, (VF_ENV_*, VF_ACT_*, VF_INT_*, ctrl_delay))
 # ... and the BPTT plugins (both persistent launches of a horizon) tests/test_chain_jit_gpu.py runs: (shape name in PREBUILD_SAC / PREBUILD,
 # (kernel-side env kind, VF_ACT_*, VF_INT_*, ctrl_delay)); the names ending in an activation are PREBUILD_ACT's (tests/test_bptt_activations_gpu.py)
@@ -113,10 +134,26 @@ PREBUILD_EVAL = [("tanh_nav", (1, 1, 0, True)), ("gate_pi", (3, 1, 0, True)), ("
                  ("tanh_nav", (1, 3, 0, True))]                                                               # ... with position actions
 
 
-def shape_of(obs_dims, extractor, pi, vf, head_dims=(4, 1), passthrough=(), acts=(1, 1)):
+def shape_of(obs_dims, extractor, pi, vf, head_dims=(4, 1), passthrough=(), acts=(1, 1), vf_extractor=None, vf_extractor_act=None):
     """(KIN, extractor widths in tiles, pi tiles, vf tiles[, (4, 4)][, ("act", trunks, extractor)]) of a network the generated chain classes
     cover, else None.  Heads (4, 1): the actor-critic of the PPO policies; (4, 4): the SAC-style Actor of BPTT / SHAC (mu / log_std heads).
-    acts: VF_ACTIVATION_* of the trunks / the extractor MLPs -- (1, 1) = ReLU networks (no element: the keys of r05's shapes)"""
+    acts: VF_ACTIVATION_* of the trunks / the extractor MLPs -- (1, 1) = ReLU networks (no element: the keys of r05's shapes).
+    vf_extractor ({key: hidden sizes}; vf_extractor_act: its activation, default the pi side's): the critic has an extractor of its own
+    (MlpPolicy ``vf_extractor``) -- `extractor` is then the pi side's, and the shape gains the element ("sep", KIN of the vf side, its
+    extractor widths in tiles, which of the network's inputs each of its branches reads, its activation).  Such a network qualifies when
+    each side alone does and the union of the two sides' observation keys is at most two inputs"""
+    if vf_extractor is not None:
+        if tuple(head_dims) != (4, 1) or passthrough or not vf_extractor:
+            return None
+        union = list(extractor) + [k for k in vf_extractor if k not in extractor]
+        if len(union) > 2:
+            return None
+        a = shape_of(obs_dims, extractor, pi, vf, acts=acts)
+        eact = int(acts[1] if vf_extractor_act is None else vf_extractor_act)
+        b = shape_of(obs_dims, vf_extractor, pi, vf)
+        if a is None or b is None:
+            return None
+        return a + (("sep", b[0], b[1], tuple(union.index(k) for k in vf_extractor), eact),)
     critic = tuple(head_dims) == (1, 1)      # td_policies.ContinuousCritic: th.cat([features, actions]) -> qf0 / qf1 (one pass-through input of <= 4 columns)
     if critic != bool(passthrough) or tuple(head_dims) not in ((4, 1), (4, 4), (1, 1)) or not 1 <= len(extractor) <= 2:
         return None
@@ -160,6 +197,14 @@ def _acts(shape):
     return 1, 1
 
 
+def _sep(shape):
+    """the ("sep", ..) element of a network with separate pi / vf extractors, else None"""
+    for e in shape[4:]:
+        if e and e[0] == "sep":
+            return e
+    return None
+
+
 _ACT_NAME = {1: "relu", 2: "tanh", 3: "elu", 4: "leaky_relu"}
 
 
@@ -167,6 +212,11 @@ def name_of(shape):
     kin, ew, pw, vw = shape[:4]
     f = lambda t: "[" + ",".join(str(32 * x) for x in t) + "]"
     a = _acts(shape)
+    sep = _sep(shape)
+    if sep:
+        return ("pi: " + " ".join(f"in{k}{f(e)}" for k, e in zip(kin, ew)) + f" pi{f(pw)} | vf: " +
+                " ".join(f"in{k}@{i}{f(e)}" for k, e, i in zip(sep[1], sep[2], sep[3])) + f" vf{f(vw)}" +
+                ("" if a == (1, 1) and sep[4] == 1 else f" act {_ACT_NAME[a[0]]}/{_ACT_NAME[a[1]]}/{_ACT_NAME[sep[4]]}"))
     return (" ".join(f"in{k}{f(e)}" for k, e in zip(kin, ew)) + f" pi{f(pw)} vf{f(vw)}" + {(4, 4): " heads 4/4", (1, 1): " (+) action, heads 1/1", (4, 1): ""}[_heads(shape)] +
             ("" if a == (1, 1) else f" act {_ACT_NAME[a[0]]}/{_ACT_NAME[a[1]]}"))
 
@@ -176,6 +226,8 @@ def source(shape):
     kin, ew, pw, vw = shape[:4]
     pad = lambda t, n=MAX_DEPTH: ", ".join(str(x) for x in (tuple(t) + (0,) * n)[:n])
     nb = len(kin)
+    if _sep(shape):
+        return _sep_source(shape)
     return f"""// generated by visfly_amd/_jit.py -- chain plugin for: {name_of(shape)}
 #define VF_CHAIN_PLUGIN 1
 #include "vf_mlp_chain_gen.hpp"
@@ -201,6 +253,49 @@ struct SpecPi : Spec {{
 using Net = vf::ChainNetG<Spec>;
 using NetPi = vf::ChainNetG<SpecPi>;
 VF_CHAIN_PLUGIN_DEFINE(Net, NetPi, "{name_of(shape)}")
+"""
+
+
+def _sep_source(shape):
+    """the translation unit of a network with separate pi / vf extractors: two single-trunk Specs -- A: pi-side extractor + pi trunk + the
+    4-wide mean head, B: vf-side extractor + vf trunk + the 1-wide value head -- placed in the common layer table
+    [pi extractor][vf extractor][pi trunk, mean][vf trunk, value] (csrc/vf_mlp_chain_sep.hpp)"""
+    kin, ew, pw, vw = shape[:4]
+    _, kin_v, ew_v, in_v, eact_v = _sep(shape)
+    act, eact = _acts(shape)
+    pad = lambda t, n=MAX_DEPTH: ", ".join(str(x) for x in (tuple(t) + (0,) * n)[:n])
+
+    def spec(name, kin, ew, tw, eact):
+        nb = len(kin)
+        return f"""struct {name} {{
+    static constexpr int NB = {nb};
+    static constexpr int KIN[2] = {{{pad(kin, 2)}}};
+    static constexpr int DE[2] = {{{pad([len(e) for e in ew], 2)}}};
+    static constexpr int EW[2][{MAX_DEPTH}] = {{{{{pad(ew[0])}}}, {{{pad(ew[1] if nb > 1 else ())}}}}};
+    static constexpr int DP = {len(tw)}, DV = {len(tw)};      // (one trunk: the second is never run)
+    static constexpr int PW[{MAX_DEPTH}] = {{{pad(tw)}}};
+    static constexpr int VW[{MAX_DEPTH}] = {{{pad(tw)}}};
+    static constexpr bool VF = false;
+    static constexpr int HM = 4, HV = 1;
+    static constexpr int PASS = 0;
+    static constexpr int ACT = {act}, EACT = {eact};
+}};
+"""
+    n_a, n_b = sum(len(e) for e in ew), sum(len(e) for e in ew_v)
+    n_all = n_a + n_b + len(pw) + 1 + len(vw) + 1
+    in_a = tuple(range(len(kin)))
+    idx = lambda t: ", ".join(str(x) for x in (tuple(t) + (-1, -1))[:2])
+    copy_b = sum(1 << b for b, i in enumerate(in_v) if i not in in_a)       # an input both sides read is copied by role 0
+    return f"""// generated by visfly_amd/_jit.py -- chain plugin for: {name_of(shape)}
+#define VF_CHAIN_PLUGIN 1
+#include "vf_mlp_chain_sep.hpp"
+namespace {{
+{spec("SpecA", kin, ew, pw, eact)}{spec("SpecB", kin_v, ew_v, vw, eact_v)}}}  // namespace
+static_assert({n_all} <= VF_MLP_MAX_LAYERS, "layer table");
+//                     Spec, role, first extractor layer, first trunk layer, layers, inputs of branch 0 / 1, copies
+using NetA = vf::SepNet<SpecA, 0, 0, {n_a + n_b}, {n_all}, {idx(in_a)}, {(1 << len(kin)) - 1}>;
+using NetB = vf::SepNet<SpecB, 1, {n_a}, {n_a + n_b + len(pw) + 1}, {n_all}, {idx(in_v)}, {copy_b}>;
+VF_CHAIN_PLUGIN_SEP_DEFINE(NetA, NetB, "{name_of(shape)}")
 """
 
 
@@ -263,7 +358,7 @@ def _key(shape, rollout=None):
     h = hashlib.sha256()
     h.update(_source_of(shape, rollout).encode())
     h.update(" ".join(_flags()[:-4]).encode())
-    for n in _HEADERS + (() if rollout is None else _BPTT_HEADERS if _is_bptt(rollout) else _EVAL_HEADERS if _is_eval(rollout) else _ROLLOUT_HEADERS) + (os.path.join(INCLUDE, "visfly_amd.h"),):
+    for n in _HEADERS + (("vf_mlp_chain_sep.hpp",) if _sep(shape) else ()) + (() if rollout is None else _BPTT_HEADERS if _is_bptt(rollout) else _EVAL_HEADERS if _is_eval(rollout) else _ROLLOUT_HEADERS) + (os.path.join(INCLUDE, "visfly_amd.h"),):
         with open(n if os.path.isabs(n) else os.path.join(CSRC, n), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -275,6 +370,9 @@ def _slug(shape, rollout=None):
     s = "e" + "_".join(f"{k}x{t(e)}" for k, e in zip(kin, ew)) + f"_p{t(pw)}_v{t(vw)}" + {(4, 4): "_h44", (1, 1): "_h11", (4, 1): ""}[_heads(shape)]
     if _acts(shape) != (1, 1):
         s += "_a%d%d" % _acts(shape)
+    sep = _sep(shape)
+    if sep:
+        s += "_sep" + "_".join(f"{k}i{i}x{t(e)}" for k, e, i in zip(sep[1], sep[2], sep[3])) + ("" if sep[4] == 1 else f"a{sep[4]}")
     if _is_bptt(rollout):
         return s + "_bptt" + "".join(str(int(x)) for x in rollout[1:])
     if _is_eval(rollout):
@@ -361,8 +459,8 @@ def ensure(shape):
 
 def ensure_rollout(shape, cfg):
     """the same for the roll-out plugin of `shape` under cfg = (env kind, action type, integrator, ctrl_delay)"""
-    if shape is None or is_builtin(shape) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
-        return False
+    if shape is None or is_builtin(shape) or _sep(shape) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
+        return False         # (separate pi / vf extractors: no persistent launch -- the trainers step launch by launch)
     key = (shape, tuple(int(x) for x in cfg))
     if key not in _loaded:
         from . import _lib
@@ -376,7 +474,7 @@ def ensure_rollout(shape, cfg):
 def ensure_bptt(shape, cfg):
     """the same for the BPTT plugin (the two persistent launches of a horizon) of an actor class `shape` under cfg = (KERNEL-side env kind,
     action type, integrator, ctrl_delay); ~2 min of hipcc on first use"""
-    if shape is None or is_builtin(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
+    if shape is None or is_builtin(shape) or _sep(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
         return False
     key = (shape, ("bptt",) + tuple(int(x) for x in cfg))
     if key not in _loaded:
@@ -391,7 +489,7 @@ def ensure_bptt(shape, cfg):
 def ensure_eval(shape, cfg):
     """the same for the evaluation plugin (the deterministic-episode launch of visfly_amd.evaluate) of a class with a 4-wide mean head under
     cfg = (KERNEL-side env kind, action type, integrator, ctrl_delay)"""
-    if shape is None or is_builtin(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
+    if shape is None or is_builtin(shape) or _sep(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
         return False
     key = (shape, ("eval",) + tuple(int(x) for x in cfg))
     if key not in _loaded:
@@ -404,7 +502,11 @@ def ensure_eval(shape, cfg):
 
 
 def prebuild_shape(name):
-    """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC / PREBUILD_CRITIC, or of PREBUILD_ACT (with its activations)"""
+    """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC / PREBUILD_CRITIC, or of PREBUILD_ACT (with its activations);
+    or an entry of PREBUILD_SEP"""
+    if name in PREBUILD_SEP:
+        v = PREBUILD_SEP[name]
+        return shape_of(*v[:4], acts=v[5][:2], vf_extractor=v[4], vf_extractor_act=v[5][2])
     if name in PREBUILD_ACT:
         v = PREBUILD_ACT[name]
         return shape_of(*v[:5], acts=v[5])
@@ -415,7 +517,7 @@ def prebuild(verbose=False):
     """compile the PREBUILD shapes (in parallel) -> paths"""
     act = [shape_of(*v[:5], acts=v[5]) for v in PREBUILD_ACT.values()]
     jobs = ([(shape_of(*v), None) for v in list(PREBUILD.values()) + list(PREBUILD_SAC.values()) + list(PREBUILD_CRITIC.values())] +
-            [(sh, None) for sh in act] +
+            [(sh, None) for sh in act] + [(prebuild_shape(n), None) for n in PREBUILD_SEP] +
             [(shape_of(*PREBUILD[n]), cfg) for n, cfg in PREBUILD_ROLLOUT] + [(act[0], (1, 1, 0, True))] +       # + the Tanh policy's roll-out on NavigationEnv
             [(prebuild_shape(n), ("bptt",) + cfg) for n, cfg in PREBUILD_BPTT] +
             [(prebuild_shape(n), ("eval",) + cfg) for n, cfg in PREBUILD_EVAL])

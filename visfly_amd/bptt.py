@@ -164,6 +164,9 @@ class BPTT:
             pk["net_arch"] = dict({k: v for k, v in na.items() if k != "qf"}, pi=list(na["pi"]), vf=list(na["pi"]))    # (flags such as pi_ln stay)
         # share_features_extractor=True (td_policies.py:127, SACPolicy._build): the critic runs the ACTOR's extractor under no_grad.  BPTT has
         # no critic (nothing changes); SHAC reads the flag (shac.py: _share_extractor)
+        if pk.get("pi_features_extractor_class") is not None or pk.get("vf_features_extractor_class") is not None:
+            raise NotImplementedError(f"{type(self).__name__}: pi_features_extractor_class / vf_features_extractor_class (separate pi / vf "
+                                      "feature extractors of the actor-critic policy) are not implemented for the td policies; PPO runs them")
         self._share_extractor = bool(pk.pop("share_features_extractor", False))
         if any(k in pk for k in ("features_extractor_class", "net_arch", "features_extractor_kwargs", "activation_fn")):
             pk.setdefault("activation_fn", "relu")                    # MTDPolicy's default activation IS ReLU (td_policies.py:297)
@@ -191,6 +194,10 @@ class BPTT:
     def _activations(self, pk):
         """(trunk, extractor) VF_ACTIVATION_* of translated policy_kwargs; refuses what this trainer does not run"""
         from .ppo import activation_kind
+        if pk.get("vf_extractor"):
+            raise NotImplementedError(f"{type(self).__name__}: separate pi / vf feature extractors (share_features_extractor=False of the "
+                                      "actor-critic policy, pi_features_extractor_class / vf_features_extractor_class) are not implemented: "
+                                      "this trainer's actor has no critic side; PPO runs such networks")
         if pk.get("layer_norm"):
             raise NotImplementedError(f"{type(self).__name__}: layer norm (ln / pi_ln / vf_ln, layer_norm={pk['layer_norm']}) is not implemented: "
                                       "the horizon kernels have no normalisation step; PPO runs networks with LayerNorm")

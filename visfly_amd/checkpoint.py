@@ -55,9 +55,35 @@ def extractor_keys(pk: Optional[dict], obs_keys: List[str]) -> tuple:
     An unknown class name gives () -- the translation raises for it"""
     pk = pk or {}
     if "extractor" in pk:
-        return tuple(pk["extractor"].keys())
+        return tuple(pk["extractor"].keys()) + tuple(k for k in (pk.get("vf_extractor") or {}) if k not in pk["extractor"])
+    name = lambda c: c if isinstance(c, str) else c.__name__
+    if pk.get("features_extractor_class") is None and (pk.get("pi_features_extractor_class") is not None or
+                                                        pk.get("vf_features_extractor_class") is not None):
+        # separate pi / vf extractor classes: the union of both sides' keys, the pi side's first
+        sides = [_EXTRACTORS.get(name(pk[k]), ()) for k in ("pi_features_extractor_class", "vf_features_extractor_class") if pk.get(k) is not None]
+        return tuple(dict.fromkeys(k for side in sides for k in side))
     cls = pk.get("features_extractor_class", "StateTargetExtractor" if "target" in obs_keys else "StateExtractor")
-    return _EXTRACTORS.get(cls if isinstance(cls, str) else cls.__name__, ())
+    return _EXTRACTORS.get(name(cls), ())
+
+
+def _separate_sides(pk):
+    """the reference policy's own rules about its extractor arguments (policies.py:132-138) -> None for a network with ONE extractor
+    class (shared, or instantiated twice by share_features_extractor=False), else ((pi class, pi kwargs), (vf class, vf kwargs)).
+    What its asserts refuse is a ValueError here"""
+    pic, vfc = pk.get("pi_features_extractor_class"), pk.get("vf_features_extractor_class")
+    if "features_extractor_class" in pk and pk["features_extractor_class"] is None or \
+            ("features_extractor_class" not in pk and (pic is not None or vfc is not None)):
+        if pic is None or vfc is None:
+            raise ValueError("features_extractor_class=None needs both pi_features_extractor_class and vf_features_extractor_class "
+                             "(policies.py:133)")
+        if pk.get("share_features_extractor", True):
+            raise ValueError("pi_features_extractor_class / vf_features_extractor_class need share_features_extractor=False "
+                             "(policies.py:136)")
+        return (pic, pk.get("pi_features_extractor_kwargs")), (vfc, pk.get("vf_features_extractor_kwargs"))
+    if pic is not None or vfc is not None:
+        raise ValueError("pi_features_extractor_class / vf_features_extractor_class next to features_extractor_class: the reference "
+                         "takes one or the other (policies.py:138)")
+    return None
 
 
 def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dict:
@@ -67,6 +93,9 @@ def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dic
     if "extractor" in pk:       # already MlpPolicy arguments
         return pk
     out: Dict[str, object] = {}
+    sep = _separate_sides(pk)
+    if sep is not None:        # pi_features_extractor_class / vf_features_extractor_class: the pi side takes the shared extractor's place below
+        pk["features_extractor_class"], pk["features_extractor_kwargs"] = sep[0]
     cls = pk.get("features_extractor_class", "StateTargetExtractor" if "target" in obs_keys else "StateExtractor")
     cls = cls if isinstance(cls, str) else cls.__name__
     if cls not in _EXTRACTORS:
@@ -112,7 +141,29 @@ def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dic
     if "log_std_init" in pk:
         out["log_std_init"] = float(pk["log_std_init"])
     if pk.get("share_features_extractor", True) is False:
-        raise NotImplementedError("separate pi / vf feature extractors are not implemented")
+        # SB3 ActorCriticPolicy: a second instance of the same class and kwargs for the critic; or the vf side's own class / kwargs
+        if out.get("layer_norm", {}).get("extractor") and any(out["layer_norm"]["extractor"].values()):
+            raise NotImplementedError("layer norm (ln) in the extractor MLPs of a network with separate pi / vf feature extractors is not implemented")
+        vcls, vkw = sep[1] if sep is not None else (cls, pk.get("features_extractor_kwargs"))
+        vcls = vcls if isinstance(vcls, str) else vcls.__name__
+        if vcls not in _EXTRACTORS:
+            raise NotImplementedError(f"vf_features_extractor_class {vcls}: only the vector extractors {sorted(_EXTRACTORS)} are on the "
+                                      "visual=False path")
+        missing = [k for k in _EXTRACTORS[vcls] if k not in obs_keys]
+        if missing:
+            raise ValueError(f"{vcls} (vf side) needs observation keys {missing}")
+        varch = (vkw or {}).get("net_arch") or {}
+        vext = {}
+        for k in _EXTRACTORS[vcls]:
+            a = varch.get(k) or {}
+            if a.get("bn"):
+                raise NotImplementedError("batch norm in the extractor MLPs is not implemented")
+            if a.get("ln"):
+                raise NotImplementedError("layer norm (ln) in the extractor MLPs of a network with separate pi / vf feature extractors is not implemented")
+            vext[k] = list(a.get("layer", [])) or [128, 64]          # (no net_arch: the trainers' default per key)
+        out.setdefault("extractor", {k: [128, 64] for k in _EXTRACTORS[cls]})
+        out["vf_extractor"] = vext
+        out["vf_extractor_activation"] = activation_kind((vkw or {}).get("activation_fn", "relu"))
     wd = (pk.get("optimizer_kwargs") or {}).get("weight_decay")
     if wd is not None:
         out["weight_decay"] = float(wd)
@@ -127,12 +178,16 @@ def _names(policy):
         if ly.dst in _HEAD_NAMES:
             out.append((ly, [_HEAD_NAMES[ly.dst]]))
             continue
-        if ly.first or ly.src.startswith("x:") or ly.dst == "feat":
-            key = ly.src.split(":")[1] if ly.src.startswith(("obs:", "x:")) else None
-            i = idx.get(("ext", key), 0)
-            idx[("ext", key)] = i + 1
-            out.append((ly, [f"{p}.{key}_extractor.{(3 if ly.ln else 2) * i}" for p in ("features_extractor", "pi_features_extractor",
-                                                                                         "vf_features_extractor")]))
+        if ly.ext:
+            key = ly.src.split(":")[1] if ly.src.startswith(("obs:", "x:", "vx:")) else None
+            i = idx.get(("ext", ly.side, key), 0)
+            idx[("ext", ly.side, key)] = i + 1
+            # separate extractors: the pi side is pi_features_extractor -- and features_extractor, which SB3 registers as the same module
+            # with share_features_extractor=False (with pi / vf classes of their own the reference keeps it as a module of the pi class
+            # that no forward reads: written as a copy, never preferred on load) -- the vf side vf_features_extractor alone
+            pre = {None: ("features_extractor", "pi_features_extractor", "vf_features_extractor"),
+                   "pi": ("pi_features_extractor", "features_extractor"), "vf": ("vf_features_extractor",)}[ly.side]
+            out.append((ly, [f"{p}.{key}_extractor.{(3 if ly.ln else 2) * i}" for p in pre]))
             continue
         trunk = ly.dst.split(":")[0]
         i = idx.get(trunk, 0)
@@ -224,7 +279,7 @@ def _param_order(policy):
     action_net, value_net; log_std is registered first in ActorCriticPolicy._build): -> [(offset, shape)]"""
     order = [(policy.log_std_off, (policy.n_params - policy.log_std_off,))]
     named = _names(policy)
-    rank = lambda pre: (0 if pre.startswith("features_extractor") else 1 if pre.startswith("mlp_extractor.policy") else
+    rank = lambda pre: (0 if "features_extractor" in pre else 1 if pre.startswith("mlp_extractor.policy") else
                         2 if pre.startswith("mlp_extractor.value") else 3 if pre == "action_net" else 4)
     for ly, prefixes in sorted(named, key=lambda x: rank(x[1][0])):
         order += [(ly.w_off, (ly.No, ly.K)), (ly.b_off, (ly.No,))]
@@ -272,6 +327,23 @@ def check_layer_norm(policy, spec):
             (have["pi"], have["vf"], sorted(k for k, v in have["extractor"].items() if v)):
         raise ValueError(f"the archive holds a network with layer_norm {want}, this trainer's policy has {have}: pass the archive's "
                          "ln / pi_ln / vf_ln flags (or use load(), which reads them)")
+
+
+def check_separate_extractors(policy, spec):
+    """like check_activations: an archive's spec and the policy must agree about the critic's own extractor (``vf_extractor``) --
+    ValueError otherwise, before any tensor is compared"""
+    if not isinstance(spec, dict) or "extractor" not in spec:
+        return
+    want, have = spec.get("vf_extractor"), policy.spec.get("vf_extractor")
+    norm = lambda e: None if e is None else {k: list(v) for k, v in e.items()}
+    if norm(want) != norm(have):
+        raise ValueError(f"the archive holds a network with vf_extractor {want} (None: one shared feature extractor), this trainer's policy "
+                         f"has {have}: pass the archive's share_features_extractor / vf_features_extractor_class (or use load(), which "
+                         "reads them)")
+    if want is not None and spec.get("vf_extractor_activation", spec.get("extractor_activation", "relu")) != \
+            policy.spec.get("vf_extractor_activation", policy.spec.get("extractor_activation", "relu")):
+        raise ValueError(f"the archive's vf extractor runs {spec.get('vf_extractor_activation')}, this trainer's policy "
+                         f"{policy.spec.get('vf_extractor_activation')}")
 
 
 def _hyper(trainer) -> dict:
@@ -356,6 +428,10 @@ def ctor_kwargs_from_archive(path: str, overrides: Optional[dict] = None) -> dic
                                        extractor_activation=spec.get("extractor_activation", "relu"))
             if spec.get("layer_norm"):
                 kw["policy_kwargs"]["layer_norm"] = spec["layer_norm"]
+            if spec.get("vf_extractor"):
+                kw["policy_kwargs"]["vf_extractor"] = spec["vf_extractor"]
+                if spec.get("vf_extractor_activation"):
+                    kw["policy_kwargs"]["vf_extractor_activation"] = spec["vf_extractor_activation"]
     kw.update(overrides or {})
     return kw
 
@@ -369,6 +445,7 @@ def load_into(trainer, path: str, load_optimizer: bool = True):
         check_activations(pol, data.get("policy_spec"))
     if isinstance(data, dict):
         check_layer_norm(pol, data.get("policy_spec"))
+        check_separate_extractors(pol, data.get("policy_spec"))
     load_policy_state_dict(pol, sd, strict=True)
     if load_optimizer and opt and opt.get("state"):
         order = _param_order(pol)

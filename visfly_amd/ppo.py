@@ -100,6 +100,10 @@ class _Linear:
         # nn.LayerNorm(No, eps=1e-3) between the Linear and its activation (create_mlp's ``ln``): gamma / beta sit right behind the
         # layer's own bias in ``flat`` (g_off, be_off); ``ln_key`` names the layer's pre-norm / rstd buffers
         self.ln, self.g_off, self.be_off, self.ln_key = False, None, None, None
+        # separate pi / vf extractors (MlpPolicy ``vf_extractor``): the side of the network the layer belongs to ("pi" / "vf"); None in a
+        # network with a shared extractor, whose extractor layers serve both trunks
+        self.side = None
+        self.ext = False          # a layer of an extractor MLP (either side's)
 
 
 class MlpPolicy:
@@ -115,7 +119,7 @@ class MlpPolicy:
     def __init__(self, obs_dims: Dict[str, int], extractor: Dict[str, List[int]], pi: List[int], vf: List[int],
                  device, action_dim: int = 4, log_std_init: float = 0.0, seed: int = 0, ortho_init: bool = True,
                  head_dims=None, passthrough=(), log_std_param: bool = True, activation="relu", extractor_activation="relu",
-                 layer_norm=None):
+                 layer_norm=None, vf_extractor=None, vf_extractor_activation=None):
         """``head_dims`` (default (action_dim, 1)): widths of the two heads "mean" / "value" -- the SHAC actor of the reference
         has two 4-wide heads (mu and a state-dependent log_std, utils/policies/td_policies.py:230-243), its twin critic two
         1-wide ones.  ``passthrough``: input keys whose columns are appended to the features unchanged, after the extractor
@@ -132,11 +136,34 @@ class MlpPolicy:
         Linear of that MLP and its activation; the heads are never normalised.  gamma (ones) and beta (zeros) follow the layer's own
         weight and bias in ``flat``: W, b, gamma, beta.  Such a network has no fused plan: it runs layer by layer on vf_linear_* with
         vf_layernorm_* in between (csrc/vf_layernorm.hip).  None / all flags false: the network, its parameter layout and its path
-        are exactly what they are without the argument."""
+        are exactly what they are without the argument.
+        ``vf_extractor`` ({obs key: hidden sizes}, like ``extractor``) [+ ``vf_extractor_activation``, default: the pi side's]: the
+        critic gets a feature extractor of its own -- the reference's ``share_features_extractor=False`` (SB3 builds a second instance
+        of the extractor class) and its ``pi_features_extractor_class`` / ``vf_features_extractor_class`` (policies.py:117-175: the two
+        sides may differ in class and net_arch, e.g. an asymmetric critic that also reads "target").  ``extractor`` then feeds the pi
+        trunk only (buffers ``x:<key>:<i>`` / ``feat`` as ever), ``vf_extractor`` the vf trunk only (``vx:<key>:<i>`` / ``vfeat``);
+        ``flat`` holds: pi extractor layers, vf extractor layers, pi trunk + mean head, vf trunk + value head, log_std; ``obs_keys`` =
+        the pi side's keys, then the keys only the vf side reads.  Actor-critic heads (4, 1) with the log_std parameter only, without
+        pass-through inputs and LayerNorm.  Two independent pipelines: on the chain kernels they are the two waves of one workgroup
+        (csrc/vf_mlp_chain_sep.hpp; generated on first use like any non-default shape).  None: the network, its parameter layout, its
+        spec and its path are exactly what they are without the argument."""
         assert action_dim == 4, "the head kernels are written for the 4-d drone action"
         self.device = th.device(device)
         self.passthrough = [k for k in passthrough]
-        self.obs_keys = list(extractor.keys()) + self.passthrough
+        self.sep = vf_extractor is not None
+        if self.sep:
+            hd = tuple(head_dims) if head_dims is not None else (action_dim, 1)
+            bad = [n for n, c in (("passthrough inputs", bool(self.passthrough)), (f"head_dims {hd}", hd != (4, 1)),
+                                  ("log_std_param=False", not log_std_param),
+                                  ("layer_norm", bool(layer_norm) and (any((layer_norm.get("extractor") or {}).values()) or
+                                                                        layer_norm.get("pi") or layer_norm.get("vf")))) if c]
+            if bad:
+                raise NotImplementedError(f"vf_extractor (separate pi / vf feature extractors) with {', '.join(bad)} is not implemented: "
+                                          "the PPO actor-critic (heads (4, 1), log_std parameter) without pass-through inputs or LayerNorm only")
+            if not vf_extractor:
+                raise ValueError("vf_extractor: at least one observation branch")
+            vf_extractor = {k: list(v) for k, v in vf_extractor.items()}
+        self.obs_keys = list(extractor.keys()) + self.passthrough + [k for k in (vf_extractor or {}) if k not in extractor]
         self.obs_dims = {k: int(obs_dims[k]) for k in self.obs_keys}
         self.head_dims = tuple(head_dims) if head_dims is not None else (action_dim, 1)
         self.act, self.ext_act = activation_kind(activation), activation_kind(extractor_activation)
@@ -144,6 +171,11 @@ class MlpPolicy:
         if (self.act, self.ext_act) != (1, 1):        # (archives of ReLU networks keep the r05 spec)
             self.spec.update(activation=_TORCH_ACT[self.act].lower().replace("leakyrelu", "leaky_relu"),
                              extractor_activation=_TORCH_ACT[self.ext_act].lower().replace("leakyrelu", "leaky_relu"))
+        self.vf_ext_act = self.ext_act if vf_extractor_activation is None else activation_kind(vf_extractor_activation)
+        if self.sep:
+            self.spec["vf_extractor"] = {k: list(v) for k, v in vf_extractor.items()}
+            if self.vf_ext_act != self.ext_act:
+                self.spec["vf_extractor_activation"] = _TORCH_ACT[self.vf_ext_act].lower().replace("leakyrelu", "leaky_relu")
         ln = dict(layer_norm or {})
         unknown = set(ln) - {"extractor", "pi", "vf"} | set(ln.get("extractor") or {}) - set(extractor)
         if unknown:
@@ -181,26 +213,49 @@ class MlpPolicy:
                 if not last:
                     self.widths[dst] = h
                 add(K, h, self.ext_act, src, sc, dst, dc, first=(li == 0), ln=ln_ext[k])
+                self.layers[-1].ext = True
                 src, sc, K = dst, dc, h
             col += hidden[-1]
+        # the vf side's extractor: buffers of its own (vx:<key>:<i>, vfeat); no buffer of either side has two readers
+        vfeat_w, col_v = 0, 0
+        if self.sep:
+            vfeat_w = self.widths["vfeat"] = sum(v[-1] for v in vf_extractor.values() if v)
+            for ly in self.layers:
+                ly.side = "pi"
+            for k, hidden in vf_extractor.items():
+                src, sc, K = "obs:" + k, 0, self.obs_dims[k]
+                if not hidden:
+                    raise NotImplementedError("identity extractor branches are not supported")
+                for li, h in enumerate(hidden):
+                    last = li == len(hidden) - 1
+                    dst = "vfeat" if last else f"vx:{k}:{li}"
+                    dc = col_v if last else 0
+                    if not last:
+                        self.widths[dst] = h
+                    add(K, h, self.vf_ext_act, src, sc, dst, dc, first=(li == 0))
+                    self.layers[-1].ext, self.layers[-1].side = True, "vf"
+                    src, sc, K = dst, dc, h
+                col_v += hidden[-1]
         pass_cols = []
         for k in self.passthrough:
             pass_cols.append((k, col))
             col += self.obs_dims[k]
         for trunk, hidden, head_dim, head in (("pi", pi, self.head_dims[0], "mean"), ("vf", vf, self.head_dims[1], "value")):
-            src, sc, K = "feat", 0, feat_w
+            src, sc, K = ("vfeat", 0, vfeat_w) if self.sep and trunk == "vf" else ("feat", 0, feat_w)
             for li, h in enumerate(hidden):
                 dst = f"{trunk}:{li}"
                 self.widths[dst] = h
                 add(K, h, self.act, src, sc, dst, 0, ln=ln_trunk[trunk])
+                self.layers[-1].side = trunk if self.sep else None
                 src, sc, K = dst, 0, h
             self.widths[head] = head_dim
             add(K, head_dim, 0, src, sc, head, 0)
+            self.layers[-1].side = trunk if self.sep else None
         self.log_std_off = off
         self.n_params = off + (action_dim if log_std_param else 0)      # trainable parameters (what Adam / the all-reduce see)
         # frozen identity layers of the pass-through inputs: executed with the extractors, parameters behind the trainable ones
         off = self.n_params
-        n_ext = sum(len(v) for v in extractor.values())
+        n_ext = sum(len(v) for v in extractor.values()) + sum(len(v) for v in (vf_extractor or {}).values())
         for j, (k, c) in enumerate(pass_cols):
             d = self.obs_dims[k]
             ly = _Linear(d, d, 0, "obs:" + k, 0, "feat", c, off, off + d * d, True)
@@ -252,8 +307,12 @@ class MlpPolicy:
         # chain kernels of a shape the library holds no instance of: compiled on first use (visfly_amd/_jit.py)
         # (heads (4, 1) with the log_std parameter: the PPO policies' actor-critic; (4, 4) without: the SAC-style Actor of BPTT / SHAC;
         # (1, 1) without, behind a pass-through action input: its twin critic)
-        self.chain_shape = (_jit.shape_of(self.obs_dims, extractor, pi, vf, self.head_dims, self.passthrough, acts=(self.act, self.ext_act))
-                            if bool(log_std_param) == (self.head_dims == (4, 1)) else None)
+        if self.sep:
+            self.chain_shape = _jit.shape_of(self.obs_dims, extractor, pi, vf, self.head_dims, self.passthrough, acts=(self.act, self.ext_act),
+                                             vf_extractor=vf_extractor, vf_extractor_act=self.vf_ext_act)
+        else:
+            self.chain_shape = (_jit.shape_of(self.obs_dims, extractor, pi, vf, self.head_dims, self.passthrough, acts=(self.act, self.ext_act))
+                                if bool(log_std_param) == (self.head_dims == (4, 1)) else None)
         self.chain_jit = False
         if self._plan is None:          # more activation buffers than a vf_mlp_desc names (VF_MLP_MAX_BUFS): layer-by-layer launches
             self.chain_shape = None
@@ -587,9 +646,9 @@ class MlpPolicy:
         for ly in reversed(self.layers):
             if ly.frozen:
                 continue
-            if d_value is None and (ly.dst == "value" or ly.dst.startswith("vf:")):
+            if d_value is None and (ly.dst == "value" or ly.dst.startswith("vf:") or ly.side == "vf"):
                 continue
-            if d_mean is None and (ly.dst == "mean" or ly.dst.startswith("pi:")):
+            if d_mean is None and (ly.dst == "mean" or ly.dst.startswith("pi:") or ly.side == "pi"):
                 continue
             dY = gbuf.get(ly.dst, b.get("g:" + ly.dst))
             Y, X = b[ly.dst], b[ly.src]
@@ -643,9 +702,9 @@ class MlpPolicy:
         for ly in reversed(self.layers):
             if ly.frozen:
                 continue
-            if d_value is None and (ly.dst == "value" or ly.dst.startswith("vf:")):
+            if d_value is None and (ly.dst == "value" or ly.dst.startswith("vf:") or ly.side == "vf"):
                 continue
-            if d_mean is None and (ly.dst == "mean" or ly.dst.startswith("pi:")):
+            if d_mean is None and (ly.dst == "mean" or ly.dst.startswith("pi:") or ly.side == "pi"):
                 continue
             dY = gbuf.get(ly.dst, b.get("g:" + ly.dst))
             Y, X = b[ly.dst], b[ly.src]
@@ -746,7 +805,7 @@ class MlpPolicy:
         """indices of the (mean, value) head layers in the reverse layer table ``_bwd_desc`` builds (reversed layer order, a
         trunk without head gradient skipped)"""
         order = [ly.dst for ly in reversed(self.layers)
-                 if not ly.frozen and (both_heads or not (ly.dst == "value" or ly.dst.startswith("vf:")))]
+                 if not ly.frozen and (both_heads or not (ly.dst == "value" or ly.dst.startswith("vf:") or ly.side == "vf"))]
         return order.index("mean"), (order.index("value") if both_heads else None)
 
     def backward_data(self, d_mean, slot, d_value=None):
@@ -798,7 +857,7 @@ class MlpPolicy:
     def bucket_split(self):
         """first flat-parameter offset of the trunks: [0, split) = the extractor MLPs' parameters, [split, n_params) = both trunks, the
         heads and log_std -- the two gradient buckets of the two-bucket exchange (PPO.grad_buckets)"""
-        return min(ly.w_off for ly in self.layers if not ly.frozen and not (ly.first or ly.src.startswith("x:") or ly.dst == "feat"))
+        return min(ly.w_off for ly in self.layers if not ly.frozen and not ly.ext)
 
     def ppo_update(self, obs, actions, old_lp, adv, ret, loss_cfg, stats, loss_scratch, want_sumsq=False, row_index=None, between=None):
         """forward + PPO loss + reverse chain in one launch, then the weight gradients into ``self.grad`` (vf_ppo_update +
@@ -809,7 +868,7 @@ class MlpPolicy:
         ``between()`` runs after the first pair was enqueued (the trainer starts the first bucket's all-reduce there).
         ``row_index`` (int64, M entries; vf_ppo_loss_cfg.row_index): obs / actions / old_lp / ret (and loss_cfg.old_value) are the
         WHOLE rollout buffer and row m of the minibatch is their row row_index[m] -- no shuffled copy; ``adv`` stays in minibatch order."""
-        if self._fused_ppo is False or self._plan is None or not (self.fused and self.fused_backward):
+        if self._fused_ppo is False or self._plan is None or not (self.fused and self.fused_backward) or (self.sep and len(self.obs_keys) > 2):
             return False
         M = actions.shape[0] if row_index is None else row_index.numel()
         b = self._buffers(M, 0)
@@ -1016,10 +1075,11 @@ class MlpPolicy:
                     if ly.ln:
                         y = s.norm[str(i)](y)
                     y = getattr(nn, _TORCH_ACT[ly.relu])()(y) if ly.relu else y
-                    if ly.dst == "feat":
-                        if "feat" not in acts:
-                            acts["feat"] = th.zeros((M, pol.widths["feat"]), dtype=y.dtype, device=y.device)
-                        acts["feat"] = th.cat([acts["feat"][:, :ly.dc], y, acts["feat"][:, ly.dc + ly.No:]], dim=1)
+                    if ly.dst in ("feat", "vfeat"):
+                        f = ly.dst
+                        if f not in acts:
+                            acts[f] = th.zeros((M, pol.widths[f]), dtype=y.dtype, device=y.device)
+                        acts[f] = th.cat([acts[f][:, :ly.dc], y, acts[f][:, ly.dc + ly.No:]], dim=1)
                     else:
                         acts[ly.dst] = y
                 s.acts = acts                   # the last pass's layer outputs by buffer name (tests read the trunks' from here)
@@ -1102,7 +1162,8 @@ class PPO:
         self.policy = MlpPolicy(obs_dims, extractor, pk.get("pi", [64, 64]), pk.get("vf", [64, 64]), self.device,
                                 log_std_init=pk.get("log_std_init", 0.0), seed=seed, ortho_init=pk.get("ortho_init", True),
                                 activation=pk.get("activation", "relu"), extractor_activation=pk.get("extractor_activation", "relu"),
-                                layer_norm=pk.get("layer_norm"))
+                                layer_norm=pk.get("layer_norm"), vf_extractor=pk.get("vf_extractor"),
+                                vf_extractor_activation=pk.get("vf_extractor_activation"))
         if self.policy.ln:
             self.policy._warn_fallback("PPO")
         self.policy.lazy_pack = True        # this trainer calls mark_updated() after every optimiser step

@@ -90,7 +90,7 @@ class SHAC(BPTT):
         # _eps_override (tests): (2H, N, 4) noise feed, [2t] = action of step t, [2t+1] = next action
 
     def _ext_layers(self):
-        return [ly for ly in self.critic.layers if not ly.frozen and (ly.dst == "feat" or ly.dst.startswith("x:"))]
+        return [ly for ly in self.critic.layers if not ly.frozen and ly.ext]
 
     def _sync_shared_extractor(self):
         """share_features_extractor: the critic's extractor parameters ARE the actor's (after every actor step)"""
