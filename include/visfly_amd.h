@@ -416,19 +416,26 @@ int vf_env_time_steps(vf_env* h, const float* action, const vf_env_out* out, int
  *                adjoint w.r.t. the state AFTER the step, on exit w.r.t. the state BEFORE it
  *   d_action     (N,4) out: dLoss/d(action)
  * Euler and (repaired) RK4 integrators, thrust / bodyrate actions, Hover / Racing (hover-style terms) and
- * NavigationEnv rewards; anything else returns VF_EINVAL.  With per-agent wind rows set (vf_dyn_set_wind) the call returns
- * VF_EUNSUPPORTED: the tape does not record the rows, and replaying the interval with the constant wind would differentiate a
- * different trajectory. */
+ * NavigationEnv rewards; anything else returns VF_EINVAL.
+ * Wind: the reverse pass replays the interval, so it needs the wind THAT step ran with.  vf_env_step_bwd / vf_dyn_step_bwd replay with
+ * the constant vf_dyn_cfg.wind; while per-agent rows are set (vf_dyn_set_wind) they return VF_EUNSUPPORTED, because the handle's rows
+ * belong to the latest step and the constant would differentiate a different trajectory.  vf_env_step_bwd_wind /
+ * vf_dyn_step_bwd_wind take the rows of the step as wind_Nx4 (N rows x, y, z, -; device memory, 16-byte aligned, else VF_EINVAL before any
+ * device work): the caller copies the rows after evaluating them for a forward step and hands the copy back here.  The wind is a
+ * constant of the step (no gradient flows into it).  wind_Nx4 == NULL is exactly the call without the suffix. */
 typedef struct vf_env_bwd_args {
     const float* tape_slab; const float* action; const float* d_obs; const float* d_reward;
     const uint8_t* done; float* adj_slab; float* d_action;
 } vf_env_bwd_args;
 int vf_env_step_bwd(vf_env* h, const vf_env_bwd_args* args, vf_stream_t stream);
+int vf_env_step_bwd_wind(vf_env* h, const vf_env_bwd_args* args, const float* wind_Nx4, vf_stream_t stream);
 /* Dynamics.step's own reverse pass: the same kernel on a bare vf_dyn handle -- no reward term, no episode ends.
  *   tape_slab copy of the slab taken BEFORE the vf_dyn_step call, action what that call was given, d_state (N,13) dLoss/d(state it
  *   returned) or NULL, adj_slab in/out as above, d_action (N,4) out.  Thrust / bodyrate actions, Euler / RK4. */
 int vf_dyn_step_bwd(vf_dyn* h, const float* tape_slab, const float* action, const float* d_state, float* adj_slab,
                     float* d_action, vf_stream_t stream);
+int vf_dyn_step_bwd_wind(vf_dyn* h, const float* tape_slab, const float* action, const float* d_state, float* adj_slab,
+                         float* d_action, const float* wind_Nx4, vf_stream_t stream);
 /* SURVEY 8b.4 also lists `*_cpu` twins of these entry points in the CPU restatement library.  The restatement (oracle/
  * vf_oracle.h, test infrastructure) keeps an ABI of its own instead -- vfo_dyn_step, vfo_env_post_step, vfo_gae, vfo_td_returns ...
  * on the reference's (C, N) row layout with host pointers -- because it restates the REFERENCE's data layout and call

@@ -242,6 +242,7 @@ SIGNATURES = {
     "vf_eval_latch": (C.c_int, [_vp] * 10 + [C.c_int32, C.c_int32, _vp]),
     "vf_eval_action": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "vf_dyn_step_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vf_dyn_step_bwd_wind": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vf_env_ring_phase": (C.c_int32, [_vp]),
     "vf_env_set_ring_phase": (C.c_int, [_vp, C.c_int32]),
     "vf_dyn_ring_phase": (C.c_int32, [_vp]),
@@ -256,6 +257,7 @@ SIGNATURES = {
     "vf_env_query": (C.c_int, [_vp, C.POINTER(EnvView), _vp]),
     "vf_env_time_steps": (C.c_int, [_vp, _vp, C.POINTER(EnvOut), C.c_int32, C.c_int32, _vp, C.POINTER(C.c_float)]),
     "vf_env_step_bwd": (C.c_int, [_vp, C.POINTER(EnvBwdArgs), _vp]),
+    "vf_env_step_bwd_wind": (C.c_int, [_vp, C.POINTER(EnvBwdArgs), _vp, _vp]),
     "vf_linear_bwd_weight_acc": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32,
                                            C.c_int32, _vp, C.c_int32, _vp]),
     "vf_gae": (C.c_int, [_vp] * 7 + [C.c_int32, C.c_int32, C.c_double, C.c_double, _vp]),

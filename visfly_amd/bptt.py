@@ -14,6 +14,11 @@ Extractors: ``StateExtractor``, ``StateTargetExtractor`` and, on the racing envs
 is fed as one float32 column holding the agent's current gate, carries no gradient (``env.backward_step`` receives d obs["state"] only),
 and on the persistent launches of a generated class comes from the index the wave holds.  Not part of this: a full ``BPTT.learn``
 fixture of the reference on the racing envs (the loop is pinned by bptt_loop_hover*, RacingEnv2's adjoint by bptt_racing2_thrust).
+
+String wind functions (``wind_settings`` of six expressions) are host lambdas re-evaluated before every step, so under them a horizon
+steps launch by launch in both directions (``rollout_policy`` / ``reverse_policy`` answer False): the tape keeps the per-agent wind rows
+of every recorded step and ``env.backward_step`` hands them to ``vf_env_step_bwd_wind``; on the reference's tape the wind is a constant
+of the step as well (fixtures ``bptt_wind_*``, ``bptt_loop_hover_wind``).
 """
 import ctypes as C
 import os

@@ -19,6 +19,11 @@ struct BwdArgs {
     float* adj;
     float4* d_action;
 };
+// the WIND instances of k_env_step_bwd: BwdArgs + N rows x, y, z, - = the wind of THAT control interval (what its forward step ran
+// with).  A struct of its own: BwdArgs, and with it every no-wind instance here and in k_bptt_reverse, stays what it was
+struct BwdArgsWind : BwdArgs {
+    const float4* wind;
+};
 
 __device__ __forceinline__ Quat qscale(const Quat& a, float s) { return Quat{a.w * s, a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ void qacc(Quat& a, const Quat& b) { a.w += b.w; a.x += b.x; a.y += b.y; a.z += b.z; }
@@ -62,6 +67,26 @@ __device__ __forceinline__ void rotate_bwd(const Quat& q, const float* x, const 
     lx[0] += lX.x; lx[1] += lX.y; lx[2] += lX.z;
 }
 
+// wind velocity of the interval the adjoint replays: the constant vf_dyn_cfg.wind, or (WIND) the agent's row of the rows that step ran
+// with.  Lanes i >= N read no row (the rows of the last recorded step may end the allocation).  Two types, so that the no-wind
+// instances hold nothing new: even a dead local array moved one k_bptt_reverse instance by a register (profiles/wind_adjoint.txt)
+template <bool WIND> struct WindRow;
+template <> struct WindRow<false> {
+    __device__ __forceinline__ WindRow(const vf_dyn_cfg&, const float4*, int, bool) {}
+    __device__ __forceinline__ const float* ptr(const vf_dyn_cfg& c) const { return c.wind; }
+};
+template <> struct WindRow<true> {
+    float v[3];
+    __device__ __forceinline__ WindRow(const vf_dyn_cfg& c, const float4* rows, int i, bool live) : v{c.wind[0], c.wind[1], c.wind[2]}
+    {
+        if (live) {
+            const float4 w = rows[i];
+            v[0] = w.x; v[1] = w.y; v[2] = w.z;
+        }
+    }
+    __device__ __forceinline__ const float* ptr(const vf_dyn_cfg&) const { return v; }
+};
+
 constexpr int kSave = 14;  // per sub-step: q(4) v(3) w(3) wm(4)
 
 // adjoint of (dq, dw) = derivs(q, w, tau)  (utils/maths.py:311,314): dq = 0.5 q (0,w), dw = Jinv (tau - w x (J w))
@@ -98,15 +123,24 @@ __device__ __forceinline__ void derivs_bwd(const vf_dyn_cfg& c, const Quat& q, c
 // QUAD (with CKPT): four lanes per agent -- the wave's 16 agents sit in QUADS (lanes 4 m .. 4 m + 3 = agent slot m; the caller passes the
 // same `i` to the four lanes of a quad) and the sub-step loop, two thirds of this function, runs in component layout
 // (vf_env_bwd_quad.hpp).  Everything outside the loop is per agent, not per component, and stays replicated.  Bit-identical.
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, int STRIDE, bool CKPT = false, bool QUAD = false>
+//
+// WIND: the interval ran with the agent's row of `wind` (string wind functions, re-evaluated on the host before every step) instead of
+// the constant vf_dyn_cfg.wind: the replay and the reward terms read that row.  On the reference's tape the wind is a constant of the
+// step (it depends on the agent's time and its own previous value only), so no adjoint flows into it.  WIND = false compiles to the
+// code without the parameter.
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, int STRIDE, bool CKPT = false, bool QUAD = false, bool WIND = false>
 __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf_env_cfg& e, const BwdArgs& g, int i, bool live, float* lds_col,
                                                    const float4* rec = nullptr, QuadCarry* carry = nullptr, const float* d_obs_lds = nullptr,
-                                                   float* d_action_lds = nullptr, const QuadLane* quad = nullptr)
+                                                   float* d_action_lds = nullptr, const QuadLane* quad = nullptr, const float4* wind = nullptr)
 {
     // QUAD: `carry` holds the adjoint of the persistent state from step to step (g.adj is not touched), the observation gradient of
     // the wave's agents comes from d_obs_lds ([16 slots][16] floats, LDS; read iff g.d_obs != nullptr), the action gradient goes to
     // d_action_lds ([16 slots] float4, LDS; g.d_action is not written)
     static_assert(!QUAD || CKPT, "the component layout reads the sub-step tape");
+    static_assert(!WIND || !CKPT, "the persistent sweep carries no wind rows");
+    // wind velocity of the interval.  Lanes i >= N read no row: the rows of the last recorded step may end the allocation
+    const WindRow<WIND> wrow(c, wind, i, live);
+    const float* wnd = wrow.ptr(c);
     float* T = const_cast<float*>(g.tape);
     Agent s;
     Spares sp;
@@ -225,7 +259,7 @@ __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf
             for (int k = 0; k < 4; ++k) sv[(10 + k) * STRIDE] = s.wm[k];
             float ft[4];
             motor_substep<CTRL_DELAY>(c, Td, wdp, s.wm, s.T, ft);
-            trans_substep<INTEG>(c, s.q, ft[0], kl, kq, c.wind, s.p, s.v, s.acc);
+            trans_substep<INTEG>(c, s.q, ft[0], kl, kq, wnd, s.p, s.v, s.acc);
             rot_substep<INTEG>(c, ft + 1, s.q, s.w, s.aa);
         }
     }
@@ -314,7 +348,7 @@ __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf
         // NavigationEnv2.get_reward (envs/NavigationEnv.py:185-224): 0.02 (v_along - |v_across|) toward the target - 0.001 |w| + success,
         // get_along_vertical_vector (:16-24): bn = base / (|base| + 1e-8), along = <v, bn>, across = v - bn along.  success is a constant.
         const float dr = dr_in;
-        const float vv[3] = {s.v[0] + c.wind[0], s.v[1] + c.wind[1], s.v[2] + c.wind[2]};
+        const float vv[3] = {s.v[0] + wnd[0], s.v[1] + wnd[1], s.v[2] + wnd[2]};
         const float base[3] = {e.target[0] - s.p[0], e.target[1] - s.p[1], e.target[2] - s.p[2]};
         const float nb = norm3(base[0], base[1], base[2]), den = nb + 1e-8f;
         const float bn[3] = {base[0] / den, base[1] / den, base[2] / den};
@@ -348,7 +382,7 @@ __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf
         // (droneEnv.py:345-366) -- the distance / direction to the closest bbox face; success and the step counter are
         // constants.  clamp / clamp_max / clamp_min pass the gradient on the closed side, relu'(0) = 0, norm'(0) = 0.
         const float dr = dr_in;
-        const float vv[3] = {s.v[0] + c.wind[0], s.v[1] + c.wind[1], s.v[2] + c.wind[2]};
+        const float vv[3] = {s.v[0] + wnd[0], s.v[1] + wnd[1], s.v[2] + wnd[2]};
         const Collision col = bbox_collision(e, s.p);
         const bool success = norm3(s.p[0] - e.target[0], s.p[1] - e.target[1], s.p[2] - e.target[2]) <= e.success_radius;
         const int step_count = __float_as_int(sp.omg) + 1;        // counter of THIS step (the tape holds the pre-step slab)
@@ -446,7 +480,7 @@ __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf
         const float np_ = norm3(dp[0], dp[1], dp[2]);
         const float dqv[4] = {s.q.w - 1.0f, s.q.x, s.q.y, s.q.z};
         const float nq = norm4(dqv[0], dqv[1], dqv[2], dqv[3]);
-        const float vv[3] = {s.v[0] + c.wind[0], s.v[1] + c.wind[1], s.v[2] + c.wind[2]};
+        const float vv[3] = {s.v[0] + wnd[0], s.v[1] + wnd[1], s.v[2] + wnd[2]};
         const float nv = norm3(vv[0], vv[1], vv[2]), nw = norm3(s.w[0], s.w[1], s.w[2]);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {

@@ -138,6 +138,12 @@ class Dynamics:
     def _wind(self):
         """(1,3) constant wind or (N,3) per-agent rows"""
         return self._wind_const if self._wind_fn is None else self._wind_rows[:, :3]
+
+    @property
+    def wind_rows(self):
+        """(N,4) rows x, y, z, - the latest step() ran with (wind functions only, else None).  Read-only: a copy -- what
+        backward_step(wind=) wants for that step"""
+        return None if self._wind_fn is None else self._wind_rows.clone()
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -223,17 +229,29 @@ class Dynamics:
             self._last_action = a
         return out
 
-    def backward_step(self, tape_slab, action, d_state, adj_slab):
+    def backward_step(self, tape_slab, action, d_state, adj_slab, wind=None):
         """reverse pass of ONE step() of a bare Dynamics object (vf_dyn_step_bwd; what autograd does through
         dynamics.py:319-372 when the loss reads the returned state): ``tape_slab`` = a clone of ``self._slab`` taken before
         that step, ``action`` what it was given, ``d_state`` (N,13) dLoss/d(returned state) or None, ``adj_slab`` the adjoint
-        of the persistent state (same shape as the slab, in/out: zeros after the last step of the horizon).  -> dLoss/d action"""
+        of the persistent state (same shape as the slab, in/out: zeros after the last step of the horizon).  With wind functions
+        ``wind`` (N,4) = a copy of ``wind_rows`` taken right after that step() call (the rows it ran with; the object's own rows
+        move on with every step; vf_dyn_step_bwd_wind).  -> dLoss/d action"""
+        if self._wind_fn is not None and wind is None:
+            raise ValueError("backward_step: these dynamics have wind functions; pass wind= a copy of the rows that step ran with "
+                             "(wind_rows.clone() taken after the step() call, before the next one)")
         with th.cuda.device(self.device):
             a = _as_device_f32(action, self.device, 4)
             d_action = th.empty((self.num, 4), dtype=th.float32, device=self.device)
             ds = None if d_state is None else d_state.to(self.device, dtype=th.float32).reshape(self.num, 13).contiguous()
-            _lib.check(_lib.lib().vf_dyn_step_bwd(self._h, _lib.ptr(tape_slab), _lib.ptr(a), _lib.ptr(ds), _lib.ptr(adj_slab),
-                                                  _lib.ptr(d_action), self._stream()))
+            if wind is None:
+                _lib.check(_lib.lib().vf_dyn_step_bwd(self._h, _lib.ptr(tape_slab), _lib.ptr(a), _lib.ptr(ds), _lib.ptr(adj_slab),
+                                                      _lib.ptr(d_action), self._stream()))
+            else:
+                w = _as_device_f32(wind, self.device, 4)
+                if w.shape[0] != self.num:
+                    raise ValueError(f"backward_step: wind must be ({self.num},4), got {tuple(w.shape)}")
+                _lib.check(_lib.lib().vf_dyn_step_bwd_wind(self._h, _lib.ptr(tape_slab), _lib.ptr(a), _lib.ptr(ds), _lib.ptr(adj_slab),
+                                                           _lib.ptr(d_action), _lib.ptr(w), self._stream()))
         return d_action
 
     # ------------------------------------------------------------------ properties

@@ -369,7 +369,7 @@ class DroneGymEnvsBase:
         self._action = th.zeros((N, 4), device=self.device)
         self._qcache = self._ext_col = None
         self._half_step = False
-        self._tape = None
+        self._tape = self._tape_wind = None
         if requires_grad:
             self.set_requires_grad(True)
         self._outs = self._out(self._terminal_obs, self._ep_return, self._ep_flags)  # obs/reward/done patched per step
@@ -612,9 +612,8 @@ class DroneGymEnvsBase:
         assert self._is_initial, "You should call reset() before step()"
         if self._half_step:
             raise VisflyError("step(): step_begin() is waiting for its step_finish()")
-        if self.envs.dynamics._wind_fn is not None:
-            if self._tape is not None:
-                raise NotImplementedError("string wind functions have no adjoint (the tape does not record the wind rows)")
+        windy = self.envs.dynamics._wind_fn is not None
+        if windy:
             self.envs.dynamics.update_wind()                                                # dynamics.py:320
         N, dev = self.num_agent, self.device
         a = _action
@@ -660,6 +659,8 @@ class DroneGymEnvsBase:
             else:
                 self._tape_action_ref[tape_t] = None
                 self._tape_actions[tape_t].copy_(a)
+            if windy:                  # the rows THIS step runs with: the dynamics' own rows belong to the latest step
+                self._tape_wind[tape_t].copy_(self.envs.dynamics._wind_rows)
             self._tape_t += 1
             self._substep_range = None        # a step recorded launch by launch: the sub-step tape no longer covers the horizon
         borrow_done = borrow and tape_t >= 0
@@ -846,6 +847,9 @@ class DroneGymEnvsBase:
         self._tape_actions = th.empty((horizon, self.num_agent, 4), dtype=th.float32, device=dev)
         self._tape_done = th.zeros((horizon, self.num_agent), dtype=th.bool, device=dev)
         self._tape_action_ref = [None] * horizon          # borrowed action tensors (see _step_no_grad)
+        # string wind functions: the per-agent rows every recorded step ran with (the wind is a constant of the step on the tape)
+        self._tape_wind = (th.zeros((horizon, self.num_agent, 4), dtype=th.float32, device=dev)
+                           if self.envs.dynamics._wind_fn is not None else None)
         self._adj = th.zeros_like(self._slab)
         self._tape_t = 0
         self._record_all = True      # manual mode: every step() is recorded until clear_tape()/detach()
@@ -1103,7 +1107,7 @@ class DroneGymEnvsBase:
         N, dev = self.num_agent, self.device
         t0 = self._tape_t - H
         nblk, blk = policy._slot_blocks.get(N, (0, None))
-        if self._tape is None or t0 < 0 or nblk < H:
+        if self._tape is None or t0 < 0 or nblk < H or self.envs.dynamics._wind_fn is not None:    # (wind rows: one launch per step)
             return False
         two_heads = d_log_stds is not None
         key = ("bwd_flat", N, H, two_heads)
@@ -1159,7 +1163,10 @@ class DroneGymEnvsBase:
                 setattr(a, name, x.data_ptr())
         a.done, a.adj_slab, a.d_action = self._tape_done[t].data_ptr(), self._adj.data_ptr(), d_action.data_ptr()
         with th.cuda.device(dev):
-            _lib.check(_lib.lib().vf_env_step_bwd(self._h, C.byref(a), self._stream()))
+            if self._tape_wind is not None:        # string wind functions: replay with the rows step t ran with
+                _lib.check(_lib.lib().vf_env_step_bwd_wind(self._h, C.byref(a), self._tape_wind[t].data_ptr(), self._stream()))
+            else:
+                _lib.check(_lib.lib().vf_env_step_bwd(self._h, C.byref(a), self._stream()))
         return d_action
 
     def time_steps(self, action, iters=100, auto_reset=True):
@@ -1226,7 +1233,7 @@ class DroneGymEnvsBase:
             self._record_all = False  # autograd mode: only graph-attached steps are recorded
             self._token = th.zeros(1, device=self.device, requires_grad=True)
         else:
-            self._tape = None
+            self._tape = self._tape_wind = None
 
     def to(self, device):
         if th.device(device).type != "cuda":

@@ -35,6 +35,8 @@ column: bptt.py).  The actor's horizons run on the persistent launches with the 
 is a generated chain class like the one-branch critic (visfly_amd/_jit.py: features (+) action <= 128 columns), its update the fused
 step (vf_twin_q_update_in3: the action rows are the third input).  The reference-default two-branch extractor ([128, 64] x 2: 132
 columns into qf0 / qf1) still runs layer by layer.
+
+Under string wind functions the actor's horizon steps launch by launch, forward and reverse (bptt.py; fixture ``shac_hover_wind``).
 """
 import ctypes as C
 from typing import Optional
