@@ -398,6 +398,19 @@ int vf_race_obs(const float* raw, const int32_t* gate, const int32_t* gate_prev,
                 const float* gates, int32_t n_gates, int32_t n_next, float radius, float* state, int32_t* gate_out, int32_t N,
                 vf_stream_t stream);
 
+/* TrackEnv's observation (envs/TrackingEnv.py:81-98) from the step kernel's raw state rows: rows_out (N, 3 n_points + 10) =
+ * [(waypoints[j] - p) / sense_radius for j < n_points, q, v / 10, w / 10] of raw (N, 13), IEEE divisions.  waypoints: HOST array
+ * (n_points, 3), 1 <= n_points <= 16, copied into the kernel arguments.  raw_term / term_out: an optional second pair of the same shapes
+ * mapped by the same launch (the terminal rows a trainer bootstraps from), both NULL or both set.  rows_out / term_out are written in
+ * 16-byte stores and must be 16-byte aligned; nothing behind row N is written.  Null pointers, n_points out of range, sense_radius <= 0,
+ * N < 1 or a misaligned output: VF_EINVAL before any launch. */
+int vf_track_obs(const float* raw, float* rows_out, const float* raw_term, float* term_out, const float* waypoints, int32_t n_points,
+                 float sense_radius, int32_t N, vf_stream_t stream);
+/* its adjoint: d_rows (N, 3 n_points + 10) -> d_raw_out (N, 13): dp[c] = -(sum_j d[3 j + c] / sense_radius), every term divided first,
+ * then added in the order j = 0, 1, ..; dq = d[3P : 3P + 4], dv = d[3P + 4 : 3P + 7] / 10, dw = d[3P + 7 : 3P + 10] / 10 (P = n_points).
+ * The waypoints carry no gradient. */
+int vf_track_obs_bwd(const float* d_rows, float* d_raw_out, int32_t n_points, float sense_radius, int32_t N, vf_stream_t stream);
+
 /* mean device microseconds per vf_env_step launch over `iters` back-to-back launches (HIP events) */
 int vf_env_time_steps(vf_env* h, const float* action, const vf_env_out* out, int32_t auto_reset, int32_t iters,
                       vf_stream_t stream, float* mean_us);

@@ -208,9 +208,13 @@ class DroneEnvsBase:
 class DroneGymEnvsBase:
     KIND = HOVER
     OBS_MODE = 0        # VF_OBS_STATE
-    _OBS_W = 13         # columns of the "state" rows the kernels write (RacingEnv2's persistent launches: 16)
+    _OBS_W = 13         # columns of the "state" rows the trainers read (RacingEnv2's persistent launches: 16; TrackEnv's launch behind the step: 40)
     REWARD_MODE = 0     # VF_REWARD_DEFAULT
     _STATIC_OBS_CONST = True   # _static_obs() returns the same tensor objects every step (the ring path caches the dict)
+    # the persistent launches (rollout_policy / reverse_policy / collect_policy / evaluate_policy_launch) exist for this env's "state" rows:
+    # 13 columns, or RacingEnv2's 16.  False (TrackEnv: 40 columns behind the step kernel): every one of them answers False before any
+    # library call -- their kernels are instantiated for the two widths above and would index such rows out of bounds
+    _PERSISTENT = True
 
     def __init__(
             self,
@@ -867,6 +871,8 @@ class DroneGymEnvsBase:
         every step in the slots' "mean" / "value" buffers.  -> False when the library has no roll-out kernel for this env / network
         / dynamics configuration (the caller then steps launch by launch).  ``reward_rows`` (H,N) / ``ep_flag_rows`` (H,N) uint8:
         optional per-step copies of the reward and of the episode flags (valid where done) -- SHAC's horizon buffer."""
+        if not self._PERSISTENT:
+            return False
         W = self._OBS_W        # 13, or the 16 gate-relative columns the persistent launches form themselves for RacingEnv2 (VF_OBS_RACE2)
         if (self._tape is None or self.spawn_mode != "device" or self._imu_noise is not None or self._half_step
                 or self.envs.dynamics._wind_fn is not None or (getattr(self, "_HOST_OBS", False) and W == 13) or not self.tensor_output
@@ -990,6 +996,8 @@ class DroneGymEnvsBase:
         terminal_rows (N, W) or None take every agent's episode as reported at its FIRST done step.  -> True, or False when the launch
         does not serve this env / network / dynamics configuration: collect_policy's conditions, except that a tape may exist (nothing is
         recorded).  Afterwards the env needs a reset() (waves leave the launch once their agents are done)."""
+        if not self._PERSISTENT:
+            return False
         W = self._OBS_W
         if (self.spawn_mode != "device" or self._imu_noise is not None or self._half_step
                 or self.envs.dynamics._wind_fn is not None or (getattr(self, "_HOST_OBS", False) and W == 13) or not self.tensor_output
@@ -1042,6 +1050,8 @@ class DroneGymEnvsBase:
         statistics -- in ONE persistent launch (vf_ppo_rollout).  buf.obs["state"][0] (and every row of buf.obs["target"])
         and buf.episode_starts[0] are the caller's.  -> the final observation TensorDict, or False when the library has no
         roll-out kernel for this env / network / dynamics configuration (the caller then steps launch by launch)."""
+        if not self._PERSISTENT:
+            return False
         W = self._OBS_W        # 13, or RacingEnv2's 16 columns (formed inside the launch: VF_OBS_RACE2)
         if (self._tape is not None or self.spawn_mode != "device" or self._imu_noise is not None or self._half_step
                 or self.envs.dynamics._wind_fn is not None or (getattr(self, "_HOST_OBS", False) and W == 13) or not self.tensor_output
@@ -1104,6 +1114,8 @@ class DroneGymEnvsBase:
         this configuration (the caller then sweeps launch by launch).  d_means (H,N,4) out, g_log_std (H,N,4) zeroed in / out.
         ``d_log_stds`` (H,N,4) out instead of g_log_std: the reference's Actor (two heads, see rollout_policy) -- both trunks are
         swept, the head gradients of every step land in d_means / d_log_stds."""
+        if not self._PERSISTENT:
+            return False
         N, dev = self.num_agent, self.device
         t0 = self._tape_t - H
         nblk, blk = policy._slot_blocks.get(N, (0, None))

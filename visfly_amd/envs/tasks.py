@@ -1,8 +1,9 @@
-"""Task envs named in BASELINE.json: HoverEnv, NavigationEnv, RacingEnv (visual=False).
+"""Task envs named in BASELINE.json: HoverEnv, NavigationEnv, RacingEnv (visual=False), and TrackEnv.
 
 Constructor kwargs follow the reference (envs/HoverEnv.py:15-30, envs/NavigationEnv.py:27-41,
-envs/RacingEnv.py:17-31); observation / reward / success definitions live in the fused kernel
-(visfly_amd/csrc/vf_env_device.hpp) and are listed next to each class.
+envs/RacingEnv.py:17-31, envs/TrackingEnv.py:15-31); observation / reward / success definitions live in the fused kernel
+(visfly_amd/csrc/vf_env_device.hpp) and are listed next to each class.  RacingEnv2 and TrackEnv form their "state" rows by one launch
+behind the step kernel (csrc/vf_obs.hip, csrc/vf_track_obs.hip).
 """
 import ctypes as C
 from typing import Optional
@@ -13,7 +14,7 @@ import torch as th
 from . import spaces
 from .. import _lib
 from ..type import TensorDict
-from .base import HOVER, NAV, RACING, DroneGymEnvsBase
+from .base import HOVER, NAV, RACING, DroneGymEnvsBase, _cuda_get_device, _raw_stream
 
 _HOVER_SPAWN = {"state_generator": {"class": "Uniform", "kwargs": [
     {"position": {"mean": [1., 0., 1.5], "half": [1.0, 1.0, 0.5]}}]}}
@@ -318,3 +319,157 @@ class RacingEnv2(RacingEnv):
 
     def _terminal_static_obs(self, i):
         return {"gate": self._terminal_gate[i].reshape(1)}
+
+
+def _track_waypoints(center, radius, radius_spd, dt, n):
+    """the (n, 3) float32 table TrackEnv.update_target forms at t == 0 (TrackingEnv.py:74-79), restated on the host: ts = k * dt and
+    radius_spd * ts in float32, cos / sin as the fp64 result rounded once (what the reference gives under the golden generator's CR-trig
+    patch, and -- for these ten arguments -- as torch runs it), then radius * c + center in float32"""
+    f = np.float32
+    ts = np.arange(n).astype(np.float32) * f(dt)
+    arg = f(radius_spd) * ts
+    c, s = np.cos(arg.astype(np.float64)).astype(np.float32), np.sin(arg.astype(np.float64)).astype(np.float32)
+    cx, cy, cz = (f(v) for v in center)
+    return np.stack([f(radius) * c + cx, f(radius) * s + cy, f(0) * s + cz], axis=1).astype(np.float32)
+
+
+class TrackEnv(DroneGymEnvsBase):
+    """obs {"state": (N, 40)} = [(next 10 waypoints of a circle - p) / max_sense_radius (30), q (4), v / 10 (3), w / 10 (3)]
+    (envs/TrackingEnv.py:14-116); success == False; reward = HoverEnv's, term for term, toward waypoint 0 (:105-116); spawn = one Uniform
+    box, mean [2, 0, 1], half [.2, .2, .2] -- the caller's random_kwargs and target are ignored, as in the reference (:39-48).
+    The reference calls update_target() once, in its constructor (t == 0), and nowhere else: the waypoints are ten constants,
+    ``env.target`` (N, 10, 3), waypoint 0 exactly [4, 0, 1].  So the step IS the HoverEnv kernel with target [4, 0, 1] (KIND = HOVER; nothing
+    new in the step kernel), and the 40 columns are formed from its raw state rows by ONE launch behind it (vf_track_obs,
+    csrc/vf_track_obs.hip), which maps the terminal rows in the same launch where a step needs both.  requires_grad=True / backward_step:
+    the rows are linear in the raw row, their adjoint is one launch (vf_track_obs_bwd) in front of the step kernel's.
+    NOT built: the register-chained kernels and the persistent launches stop at 32 input columns (visfly_amd/_jit.py: shape_of), so
+    networks over these rows run on the block-tile / per-layer kernels and every trainer steps launch by launch (``_PERSISTENT`` False);
+    step_n() is refused; a moving target (update_target() at t != 0) would make the reward per-agent while the step kernel's target is
+    one constant of vf_env_cfg -- it raises; TrackEnv2 (depth image) needs the renderer."""
+    KIND = HOVER
+    _HOST_OBS = True           # step() / step_n(): the rows are formed behind the step kernel
+    _OBS_W = 40
+    _PERSISTENT = False
+    _STATIC_OBS_CONST = False  # the ring path re-forms the rows from its slot's raw rows every step
+    _want_terminal = _terminal_fresh = False
+    _terminal_rows_wanted = False   # set by the first _terminal_state_rows() call (PPO, evaluate_policy): from then on every step maps them too
+
+    def __init__(self, num_agent_per_scene: int = 1, num_scene: int = 1, seed: int = 42, visual: bool = False,
+                 requires_grad: bool = False, random_kwargs: Optional[dict] = None, dynamics_kwargs: Optional[dict] = None,
+                 scene_kwargs: Optional[dict] = None, sensor_kwargs: Optional[list] = None, device="cuda",
+                 target=None, max_episode_steps: int = 256, latent_dim=None, tensor_output: bool = False, **kw):
+        self.center = th.as_tensor([2, 0, 1])
+        self.next_points_num = 10
+        self.radius = 2
+        self.dt = 0.1
+        self.radius_spd = 0.2 * th.pi / 1
+        self.success_radius = 0.5
+        wp = _track_waypoints(self.center.tolist(), self.radius, self.radius_spd, self.dt, self.next_points_num)
+        spawn = {"state_generator": {"class": "Uniform", "kwargs": [
+            {"position": {"mean": [float(self.center[0]), 0., float(self.center[2])], "half": [.2, .2, 0.2]}}]}}
+        super().__init__(num_agent_per_scene=num_agent_per_scene, num_scene=num_scene, seed=seed, visual=visual,
+                         requires_grad=requires_grad, random_kwargs=spawn, dynamics_kwargs=dynamics_kwargs, scene_kwargs=scene_kwargs,
+                         sensor_kwargs=sensor_kwargs, device=device, max_episode_steps=max_episode_steps,
+                         tensor_output=tensor_output, target=wp[0].tolist(), success_radius=0.5, **kw)
+        self.max_sense_radius = 10
+        self._vf_track_obs = _lib.lib().vf_track_obs
+        self._wp_host = (C.c_float * wp.size)(*[float(x) for x in wp.reshape(-1)])
+        self._wp = th.from_numpy(wp).to(self.device)
+        self.target = self._wp.unsqueeze(0).expand(self.num_envs, -1, -1).contiguous()
+        self._terminal_rows = th.zeros((self.num_agent, self._OBS_W), dtype=th.float32, device=self.device)
+        self.observation_space["state"] = spaces.Box(
+            low=-np.inf, high=np.inf,
+            shape=(3 * (self.next_points_num - 1) + self.observation_space["state"].shape[0],), dtype=np.float32)
+        self.update_target()
+
+    def update_target(self):
+        """TrackingEnv.py:74-79.  The reference calls it once, with every agent at t == 0; there it gives the constructed table and this
+        is a no-op.  At any other t it would move the waypoints per agent: the reward's target (waypoint 0) would then differ from agent
+        to agent and step to step, while the step kernel's target is ONE constant of vf_env_cfg, and none of the reference's trainers
+        or examples calls it -- not built"""
+        if bool((self.t != 0).any()):
+            raise NotImplementedError(
+                "TrackEnv.update_target() with agents at t != 0: a moved target makes the reward's target per-agent, while the step "
+                "kernel's target is one constant of vf_env_cfg; the reference itself calls update_target() only in its constructor "
+                "(t == 0), so the waypoints are the ten constants of env.target")
+
+    # ------------------------------------------------------------------ the rows
+    def _track_rows(self, raw, raw_term=None, out=None):
+        """vf_track_obs: (N, 13) raw rows -> (N, 40); raw_term: the step's terminal rows, mapped into _terminal_rows by the same launch.
+        On the step's hot path: one ctypes call, no context manager (the base step has made the env's device current already)"""
+        N, dev = raw.shape[0], self.device
+        if out is None:
+            out = th.empty((N, self._OBS_W), dtype=th.float32, device=dev)
+        if _cuda_get_device() != dev.index:
+            th.cuda.set_device(dev)
+        rc = self._vf_track_obs(raw.data_ptr(), out.data_ptr(), None if raw_term is None else raw_term.data_ptr(),
+                                None if raw_term is None else self._terminal_rows.data_ptr(), self._wp_host, self.next_points_num,
+                                float(self.max_sense_radius), N, _raw_stream(dev.index))
+        if rc:
+            _lib.check(rc)
+        return out
+
+    def _track_state(self, raw, with_terminal=False):
+        """the "state" rows of raw state rows: device batches through vf_track_obs; single rows and host tensors (the info dicts) by the
+        reference's expressions"""
+        if raw.is_cuda and raw.dim() == 2 and raw.shape[1] == 13:
+            if raw.requires_grad or raw.dtype != th.float32 or not raw.is_contiguous() or raw.device != self.device:
+                raw = raw.detach().to(self.device, dtype=th.float32).contiguous()
+            return self._track_rows(raw, self._terminal_obs if with_terminal else None)
+        one = raw.dim() == 1
+        r = raw.reshape(-1, 13)
+        wp = self._wp.to(r.device)
+        # divisors as tensors: torch's GPU kernels turn `x / python_scalar` into x * (1 / scalar), one ulp off an IEEE division
+        R, ten = th.full((1,), float(self.max_sense_radius), device=r.device), th.full((1,), 10.0, device=r.device)
+        rows = th.hstack([(wp.unsqueeze(0) - r[:, 0:3].unsqueeze(1)).reshape(r.shape[0], -1) / R, r[:, 3:7], r[:, 7:10] / ten,
+                          r[:, 10:13] / ten])                                               # TrackingEnv.py:85-94
+        return rows[0] if one else rows
+
+    def _state_obs(self, raw):
+        return self._track_state(raw)
+
+    def _full_obs(self, state, raw=False):
+        if state.shape[-1] == self._OBS_W:     # already the observation rows (step() with requires_grad: the graph-attached copy)
+            return TensorDict({"state": state})
+        wt, self._want_terminal = self._want_terminal, False
+        rows = self._track_state(state, with_terminal=wt)
+        self._terminal_fresh = wt
+        return TensorDict({"state": rows})
+
+    def _step_no_grad(self, _action, is_test=False, **kw):
+        # the step's own _full_obs call maps the live rows and -- for a caller that reads the terminal rows of every step -- the terminal
+        # rows in the same launch (they double the launch's traffic: BPTT / SHAC / plain step() loops never pay for them)
+        self._want_terminal = self._terminal_rows_wanted
+        try:
+            return super()._step_no_grad(_action, is_test=is_test, **kw)
+        finally:
+            self._want_terminal = False
+
+    def step_finish(self, *a, **kw):
+        self._want_terminal = self._terminal_rows_wanted
+        try:
+            return super().step_finish(*a, **kw)
+        finally:
+            self._want_terminal = False
+
+    def _terminal_state_rows(self):
+        self._terminal_rows_wanted = True
+        if not self._terminal_fresh:
+            self._track_rows(self._terminal_obs, out=self._terminal_rows)
+            self._terminal_fresh = True
+        return self._terminal_rows
+
+    def _terminal_state_obs(self, tobs, i):
+        return self._track_state(tobs[i])
+
+    def backward_step(self, t: int, d_obs=None, d_reward=None):
+        """d_obs (N, 40): gradient w.r.t. the observation rows step t returned -> the raw state row's (N, 13) by vf_track_obs_bwd
+        (dp = -sum_j d[3j:3j+3] / R, dq = d[30:34], dv = d[34:37] / 10, dw = d[37:40] / 10), then the step kernel's adjoint"""
+        if d_obs is not None:
+            N = self.num_agent
+            d = d_obs.to(self.device, dtype=th.float32).reshape(N, self._OBS_W).contiguous()
+            d_obs = th.empty((N, 13), dtype=th.float32, device=self.device)
+            with th.cuda.device(self.device):
+                _lib.check(_lib.lib().vf_track_obs_bwd(_lib.ptr(d), _lib.ptr(d_obs), self.next_points_num, float(self.max_sense_radius), N,
+                                                       self._stream()))
+        return super().backward_step(t, d_obs, d_reward)
