@@ -22,17 +22,20 @@ observation keys in all.  Its translation unit names two single-trunk Specs -- A
 vf-side extractor + vf trunk + the 1-wide value head -- and its forward / fused PPO step give each of two waves per 32 rows one of them
 (csrc/vf_mlp_chain_sep.hpp).  Own slug, name and cache file; never a built-in class; no roll-out, BPTT or evaluation plugin.
 
-Two more plugin kinds hold ONE instance each of a persistent launch for a generated class under one env kind / action type / integrator /
+Three more plugin kinds hold ONE instance each of a persistent launch for a generated class under one env kind / action type / integrator /
 motor-lag setting, built when a trainer first needs them: the roll-out plugin (PPO's collect_rollouts: ``ensure_rollout``,
-csrc/vf_ppo_rollout_kernel.hpp) and, r06, the BPTT plugin (both halves of a BPTT / SHAC horizon for an actor class: ``ensure_bptt``,
-csrc/vf_bptt_rollout_kernel.hpp + csrc/vf_bptt_reverse_kernel.hpp).  A third one holds the evaluation launch (deterministic episodes of
-``visfly_amd.evaluate``: ``ensure_eval``, csrc/vf_eval_rollout_kernel.hpp) of a class with a 4-wide mean head.
+csrc/vf_ppo_rollout_kernel.hpp), the BPTT plugin (both halves of a BPTT / SHAC horizon for an actor class: ``ensure_bptt``,
+csrc/vf_bptt_rollout_kernel.hpp + csrc/vf_bptt_reverse_kernel.hpp) and the evaluation plugin (deterministic episodes of
+``visfly_amd.evaluate``: ``ensure_eval``, csrc/vf_eval_rollout_kernel.hpp) of a class with a 4-wide mean head.  What tells the kinds apart
+-- slug suffix, compile parts, hashed headers, source tail, which shapes qualify -- is one row each of ``_KINDS``; the ``ensure*`` functions
+are one call each into ``_ensure``.
 """
 import hashlib
 import os
 import shutil
 import subprocess
 import tempfile
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 from ._build import CSRC, HIPCC_FLAGS, INCLUDE
@@ -127,7 +130,8 @@ PREBUILD_ROLLOUT = [("verdict", (1, 1, 0, True)), ("one_layer_extractor", (0, 1,
                     ("one_layer_extractor", (2, 1, 0, True)), ("one_layer_extractor", (3, 1, 0, True)),      # RacingEnv / RacingEnv2 (kernel-side kind 3)
                     ("gate_pi", (3, 1, 0, True)),                                                             # StateGateExtractor on RacingEnv2
                     # the geometric controller's action types (tests/test_geometric_rollout_gpu.py): velocity on HoverEnv, position on NavigationEnv2
-                    ("one_layer_extractor", (0, 2, 0, True)), ("one_layer_extractor", (1, 3, 0, True))]
+                    ("one_layer_extractor", (0, 2, 0, True)), ("one_layer_extractor", (1, 3, 0, True)),
+                    ("tanh_nav", (1, 1, 0, True))]                                                            # the Tanh default policy on NavigationEnv
 # ... and the evaluation plugins tests/test_evaluate_gpu.py runs: (shape name, (kernel-side env kind, VF_ACT_*, VF_INT_*, ctrl_delay)) -- the Tanh
 # default policy on NavigationEnv, StateGateExtractor's actor-critic on RacingEnv2, BPTT's Tanh SAC-style Actor on HoverEnv
 PREBUILD_EVAL = [("tanh_nav", (1, 1, 0, True)), ("gate_pi", (3, 1, 0, True)), ("sac_hover_tanh", (0, 1, 0, True)),
@@ -338,27 +342,47 @@ def _flags():
         "-I", INCLUDE, "-I", CSRC]
 
 
-def _is_bptt(rollout):
-    return rollout is not None and rollout[0] == "bptt"
+def _launch_ok(shape):
+    """separate pi / vf extractors: no persistent launch -- the trainers step launch by launch"""
+    return not is_builtin(shape) and not _sep(shape)
 
 
-def _is_eval(rollout):
-    return rollout is not None and rollout[0] == "eval"
+def _actor_ok(shape):
+    return _launch_ok(shape) and _heads(shape) != (1, 1)
+
+
+# one row per plugin kind: `tag` = what precedes the cfg in the `rollout` argument and in the keys of _loaded, `suffix` = what follows the
+# shape in the slug, `parts` = the -DVF_CHAIN_PLUGIN_PART values compiled, `headers` = hashed into the cache key on top of _HEADERS,
+# `source(shape, cfg)` = the translation unit, `serves(shape)` = can a generated class of this shape have such a plugin
+_Kind = namedtuple("_Kind", "tag suffix parts headers source serves")
+_KINDS = {
+    "chain": _Kind((), "", (0, 1, 2, 3), (), lambda shape, cfg: source(shape), lambda shape: not is_builtin(shape)),
+    "rollout": _Kind((), "_roll", (4,), _ROLLOUT_HEADERS, rollout_source, _launch_ok),
+    "bptt": _Kind(("bptt",), "_bptt", (5, 6, 7), _BPTT_HEADERS, bptt_source, _actor_ok),
+    "eval": _Kind(("eval",), "_eval", (8,), _EVAL_HEADERS, eval_source, _actor_ok),
+}
+
+
+def _kind_of(rollout):
+    """the `rollout` argument of build / path_of -- None (the chain plugin), (kind, act, integ, delay) (PPO's roll-out plugin),
+    ("bptt", kind, act, integ, delay) or ("eval", kind, act, integ, delay) -- as (row of _KINDS, cfg)"""
+    if rollout is None:
+        return _KINDS["chain"], ()
+    if rollout[0] in ("bptt", "eval"):
+        return _KINDS[rollout[0]], tuple(rollout[1:])
+    return _KINDS["rollout"], tuple(rollout)
 
 
 def _source_of(shape, rollout):
-    """rollout: None (the chain plugin), (kind, act, integ, delay) (PPO's roll-out plugin), ("bptt", kind, act, integ, delay) or
-    ("eval", kind, act, integ, delay)"""
-    if _is_eval(rollout):
-        return eval_source(shape, rollout[1:])
-    return source(shape) if rollout is None else bptt_source(shape, rollout[1:]) if _is_bptt(rollout) else rollout_source(shape, rollout)
+    k, cfg = _kind_of(rollout)
+    return k.source(shape, cfg)
 
 
 def _key(shape, rollout=None):
     h = hashlib.sha256()
     h.update(_source_of(shape, rollout).encode())
     h.update(" ".join(_flags()[:-4]).encode())
-    for n in _HEADERS + (("vf_mlp_chain_sep.hpp",) if _sep(shape) else ()) + (() if rollout is None else _BPTT_HEADERS if _is_bptt(rollout) else _EVAL_HEADERS if _is_eval(rollout) else _ROLLOUT_HEADERS) + (os.path.join(INCLUDE, "visfly_amd.h"),):
+    for n in _HEADERS + (("vf_mlp_chain_sep.hpp",) if _sep(shape) else ()) + _kind_of(rollout)[0].headers + (os.path.join(INCLUDE, "visfly_amd.h"),):
         with open(n if os.path.isabs(n) else os.path.join(CSRC, n), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -373,21 +397,18 @@ def _slug(shape, rollout=None):
     sep = _sep(shape)
     if sep:
         s += "_sep" + "_".join(f"{k}i{i}x{t(e)}" for k, e, i in zip(sep[1], sep[2], sep[3])) + ("" if sep[4] == 1 else f"a{sep[4]}")
-    if _is_bptt(rollout):
-        return s + "_bptt" + "".join(str(int(x)) for x in rollout[1:])
-    if _is_eval(rollout):
-        return s + "_eval" + "".join(str(int(x)) for x in rollout[1:])
-    return s if rollout is None else s + "_roll" + "".join(str(int(x)) for x in rollout)
+    k, cfg = _kind_of(rollout)
+    return s + k.suffix + "".join(str(int(x)) for x in cfg)
 
 
 def path_of(shape, rollout=None):
-    """<cache>/libvf_chain_<shape>[_roll<cfg>]_<hash of source + headers + flags>.so"""
+    """<cache>/libvf_chain_<shape>[_roll<cfg> | _bptt<cfg> | _eval<cfg>]_<hash of source + headers + flags>.so"""
     return os.path.join(JIT_DIR, f"libvf_chain_{_slug(shape, rollout)}_{_key(shape, rollout)}.so")
 
 
 def build(shape, verbose=False, rollout=None):
-    """compile the plugin of `shape` (rollout = (kind, act, integ, delay): its roll-out plugin for that configuration) unless the cache
-    holds it -> path of the shared object"""
+    """compile the plugin of `shape` (rollout: which kind and configuration, see _kind_of; None = the chain plugin) unless the cache holds
+    it -> path of the shared object"""
     out = path_of(shape, rollout)
     if os.path.exists(out):
         return out
@@ -420,7 +441,7 @@ def build(shape, verbose=False, rollout=None):
             return obj
 
         with ThreadPoolExecutor(max_workers=4) as pool:
-            objs = list(pool.map(part, range(4) if rollout is None else [5, 6, 7] if _is_bptt(rollout) else [8] if _is_eval(rollout) else [4]))
+            objs = list(pool.map(part, _kind_of(rollout)[0].parts))
         tmp = f"{out}.{os.getpid()}.tmp"       # private name, then rename: concurrent builders (ranks) never see a torn file
         try:
             r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp], capture_output=True, text=True)
@@ -442,67 +463,48 @@ def build(shape, verbose=False, rollout=None):
     return out
 
 
+def _ensure(kind, shape, cfg=()):
+    """build (or find) and register the `kind` plugin of `shape` under cfg -> True when the library now holds it"""
+    k = _KINDS[kind]
+    if shape is None or os.environ.get("VISFLY_AMD_JIT", "1") == "0" or not k.serves(shape):
+        return False
+    rollout = k.tag + tuple(int(x) for x in cfg) or None
+    key = shape if rollout is None else (shape, rollout)
+    if key not in _loaded:
+        from . import _lib
+        _loaded[key] = None                  # (a failed build is not repeated by every policy / roll-out of this shape: the caller warns once and falls back)
+        path = build(shape, rollout=rollout)
+        _lib.check(_lib.lib().vf_chain_plugin_load(path.encode()))
+        _loaded[key] = path
+    return _loaded[key] is not None
+
+
 def ensure(shape):
-    """build (or find) and register the plugin of `shape` -> True when the library now has chain kernels for it"""
+    """build (or find; ~40 s of hipcc) and register the plugin of `shape` -> True when the library now has chain kernels for it"""
     if shape is None or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
         return False
-    if is_builtin(shape):
-        return True
-    if shape not in _loaded:
-        from . import _lib
-        _loaded[shape] = None                # (a failed build is not repeated by every policy of this shape: ~40 s of hipcc each time)
-        path = build(shape)
-        _lib.check(_lib.lib().vf_chain_plugin_load(path.encode()))
-        _loaded[shape] = path
-    return _loaded[shape] is not None
+    return is_builtin(shape) or _ensure("chain", shape)
 
 
 def ensure_rollout(shape, cfg):
     """the same for the roll-out plugin of `shape` under cfg = (env kind, action type, integrator, ctrl_delay)"""
-    if shape is None or is_builtin(shape) or _sep(shape) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
-        return False         # (separate pi / vf extractors: no persistent launch -- the trainers step launch by launch)
-    key = (shape, tuple(int(x) for x in cfg))
-    if key not in _loaded:
-        from . import _lib
-        _loaded[key] = None                  # (a failed build is not retried on every roll-out: the caller warns once and falls back)
-        path = build(shape, rollout=key[1])
-        _lib.check(_lib.lib().vf_chain_plugin_load(path.encode()))
-        _loaded[key] = path
-    return _loaded[key] is not None
+    return _ensure("rollout", shape, cfg)
 
 
 def ensure_bptt(shape, cfg):
     """the same for the BPTT plugin (the two persistent launches of a horizon) of an actor class `shape` under cfg = (KERNEL-side env kind,
     action type, integrator, ctrl_delay); ~2 min of hipcc on first use"""
-    if shape is None or is_builtin(shape) or _sep(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
-        return False
-    key = (shape, ("bptt",) + tuple(int(x) for x in cfg))
-    if key not in _loaded:
-        from . import _lib
-        _loaded[key] = None
-        path = build(shape, rollout=key[1])
-        _lib.check(_lib.lib().vf_chain_plugin_load(path.encode()))
-        _loaded[key] = path
-    return _loaded[key] is not None
+    return _ensure("bptt", shape, cfg)
 
 
 def ensure_eval(shape, cfg):
     """the same for the evaluation plugin (the deterministic-episode launch of visfly_amd.evaluate) of a class with a 4-wide mean head under
     cfg = (KERNEL-side env kind, action type, integrator, ctrl_delay)"""
-    if shape is None or is_builtin(shape) or _sep(shape) or _heads(shape) == (1, 1) or os.environ.get("VISFLY_AMD_JIT", "1") == "0":
-        return False
-    key = (shape, ("eval",) + tuple(int(x) for x in cfg))
-    if key not in _loaded:
-        from . import _lib
-        _loaded[key] = None
-        path = build(shape, rollout=key[1])
-        _lib.check(_lib.lib().vf_chain_plugin_load(path.encode()))
-        _loaded[key] = path
-    return _loaded[key] is not None
+    return _ensure("eval", shape, cfg)
 
 
 def prebuild_shape(name):
-    """the shape a PREBUILD_BPTT entry names: an entry of PREBUILD / PREBUILD_SAC / PREBUILD_CRITIC, or of PREBUILD_ACT (with its activations);
+    """the shape a PREBUILD* table names: an entry of PREBUILD / PREBUILD_SAC / PREBUILD_CRITIC, or of PREBUILD_ACT (with its activations);
     or an entry of PREBUILD_SEP"""
     if name in PREBUILD_SEP:
         v = PREBUILD_SEP[name]
@@ -515,10 +517,8 @@ def prebuild_shape(name):
 
 def prebuild(verbose=False):
     """compile the PREBUILD shapes (in parallel) -> paths"""
-    act = [shape_of(*v[:5], acts=v[5]) for v in PREBUILD_ACT.values()]
-    jobs = ([(shape_of(*v), None) for v in list(PREBUILD.values()) + list(PREBUILD_SAC.values()) + list(PREBUILD_CRITIC.values())] +
-            [(sh, None) for sh in act] + [(prebuild_shape(n), None) for n in PREBUILD_SEP] +
-            [(shape_of(*PREBUILD[n]), cfg) for n, cfg in PREBUILD_ROLLOUT] + [(act[0], (1, 1, 0, True))] +       # + the Tanh policy's roll-out on NavigationEnv
+    chains = list(PREBUILD) + list(PREBUILD_SAC) + list(PREBUILD_CRITIC) + list(PREBUILD_ACT) + list(PREBUILD_SEP)
+    jobs = ([(prebuild_shape(n), None) for n in chains] + [(prebuild_shape(n), cfg) for n, cfg in PREBUILD_ROLLOUT] +
             [(prebuild_shape(n), ("bptt",) + cfg) for n, cfg in PREBUILD_BPTT] +
             [(prebuild_shape(n), ("eval",) + cfg) for n, cfg in PREBUILD_EVAL])
     # every chain job runs four hipcc parts of fully unrolled kernels: bound the number in flight by the cores of the build box

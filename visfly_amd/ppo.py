@@ -498,6 +498,32 @@ class MlpPolicy:
         _lib.check(_lib.lib().vf_mlp_pack_weights(C.byref(self._pack_desc), _ptr(self.flat), _ptr(self._packed), self._stream()))
         self._packed_stamp = self._stamp
 
+    def forward_desc(self, M, slot, save):
+        """the vf_mlp_desc of the fused forward over buffer set (M, slot), built once per (M, slot, save); ``save`` keeps the activations"""
+        key = (M, slot, bool(save))
+        d = self._descs.get(key)
+        if d is None:
+            d = self._descs[key] = self._fused_desc(self._buffers(M, slot), save)
+        return d
+
+    def reverse_flat_desc(self, M, H, d_means, d_log_stds=None):
+        """the reverse descriptor over the first H reserved slots of M rows as ONE (H M)-row matrix, built once per (M, H, heads), with
+        the heads' gradients pointed at the caller's d_means (H, M, 4) [/ d_log_stds: both trunks are swept]
+        -> (desc, {obs key: dLoss/d obs}, (H, M, 4) action-gradient scratch)"""
+        two_heads = d_log_stds is not None
+        key = ("bwd_flat", M, H, two_heads)
+        cached = self._descs.get(key)
+        if cached is None:
+            b = {name: t[:H].reshape(-1, t.shape[-1]) for name, t in self._slot_blocks[M][1].items()}
+            d, d_in = self._bwd_desc(b, H * M, d_means.view(-1, 4), d_log_stds.view(-1, 4) if two_heads else None, True)
+            cached = self._descs[key] = (d, d_in, th.empty((H, M, 4), dtype=th.float32, device=self.device))
+        d = cached[0]
+        im, iv = self._head_entries(two_heads)
+        d.layer[im].dY = _lib.ptr(d_means)
+        if two_heads:
+            d.layer[iv].dY = _lib.ptr(d_log_stds)
+        return cached
+
     # -------------------------------------------------------------------------------------------
     def weight(self, ly):
         return self.flat[ly.w_off:ly.w_off + ly.K * ly.No].view(ly.No, ly.K)
@@ -582,10 +608,7 @@ class MlpPolicy:
                 b["obs:" + k] = t
         self._last_M, self._last_slot = M, slot
         if self._plan is not None and self.fused:
-            key = (M, slot, bool(save_activations))
-            d = self._descs.get(key)
-            if d is None:
-                d = self._descs[key] = self._fused_desc(b, save_activations)
+            d = self.forward_desc(M, slot, save_activations)
             ins = [_ptr(b["obs:" + k]) for k in self.obs_keys] + [None] * (4 - len(self.obs_keys))
             self._pack()
             skip_vf = not need_value and self._pi_only_ok
@@ -759,10 +782,7 @@ class MlpPolicy:
         ins += [None] * (2 - len(ins))
         copies += [None] * (2 - len(copies))
         self._last_M, self._last_slot = M, slot
-        key = (M, slot, True)
-        d = self._descs.get(key)
-        if d is None:
-            d = self._descs[key] = self._fused_desc(b, True)
+        d = self.forward_desc(M, slot, True)
         self._pack()
         rc = _lib.lib().vf_mlp_forward_act(C.byref(d), _ptr(self.flat), _ptr(self._packed), ins[0], ins[1], _ptr(self.log_std),
                                            _ptr(eps), _ptr(action), copies[0], copies[1], M, self._stream())
@@ -897,10 +917,7 @@ class MlpPolicy:
             loss_cfg.obs_copy0 = _ptr(b["obs:" + self.obs_keys[0]])
             loss_cfg.obs_copy1 = _ptr(b["obs:" + self.obs_keys[1]]) if len(self.obs_keys) > 1 else None
         self._last_M, self._last_slot = M, 0
-        key = (M, 0, True)
-        d = self._descs.get(key)
-        if d is None:
-            d = self._descs[key] = self._fused_desc(b, True)
+        d = self.forward_desc(M, 0, True)
         if "d:mean" not in b:
             b["d:mean"], b["d:value"] = th.empty((M, 4), dtype=th.float32, device=self.device), th.empty(M, dtype=th.float32, device=self.device)
         cached = self._descs.get(("ppo_bwd", M))
@@ -991,10 +1008,7 @@ class MlpPolicy:
             else:
                 b["obs:" + k] = t
         self._last_M, self._last_slot = M, 0
-        key = (M, 0, True)
-        d = self._descs.get(key)
-        if d is None:
-            d = self._descs[key] = self._fused_desc(b, True)
+        d = self.forward_desc(M, 0, True)
         if "d:q0" not in b:
             b["d:q0"] = th.empty((M, self.head_dims[0]), dtype=th.float32, device=self.device)
             b["d:q1"] = th.empty((M, self.head_dims[1]), dtype=th.float32, device=self.device)
