@@ -7,7 +7,7 @@ the whole horizon evicted them) and hot (a second time in a row), against the on
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from visfly_amd import ppo
+from visfly_amd import policy
 from visfly_amd.bptt import BPTT
 from visfly_amd.envs import RacingEnv
 DEV, N, H = "cuda:0", 16384, 64
@@ -17,7 +17,7 @@ algo = BPTT(env, horizon=H, gamma=0.99, learning_rate=1e-3, seed=0, policy="Mult
 algo.learn(H * N * 2)          # the slots hold a real horizon's activations / masked gradients
 torch.cuda.synchronize()
 pol = algo.policy
-shipped_split, ppo.WGRAD_SPLIT_ROWS = ppo.WGRAD_SPLIT_ROWS, H * N     # the raw launches first; the shipped split (equal runs of <= 524 288 rows) at the end
+shipped_split, policy.WGRAD_SPLIT_ROWS = policy.WGRAD_SPLIT_ROWS, H * N     # the raw launches first; the shipped split (equal runs of <= 524 288 rows) at the end
 d_mu, d_ls = torch.randn((H, N, 4), device=DEV) / N, torch.randn((H, N, 4), device=DEV) / N
 w = int(pol.n_params)
 ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -57,6 +57,6 @@ for k in (1, 2, 4, 8, 16, 32):
         hot.append(m.elapsed_time(b) * 1e3)
     c, h = min(cold), min(hot)
     print(f"{k:5d} {k * N:8d} {c:9.1f} {h:9.1f} {2.0 * w * k * N / h / 1e6:9.1f} {H / k * h:22.1f} {H / k * h / t_full:14.2f}")
-ppo.WGRAD_SPLIT_ROWS = shipped_split
+policy.WGRAD_SPLIT_ROWS = shipped_split
 full(); full()
 print(f"shipped: the horizon in equal runs of <= 524 288 rows: {min(timed(full) for _ in range(5)):8.1f} us")

@@ -32,7 +32,7 @@ for _ in range(5):
 torch.cuda.synchronize()
 L, st = _lib.lib(), pol._stream()
 d = pol._descs[(M, 0, True)]
-bd, firsts = pol._descs[("ppo_bwd", M)]
+bd = pol._descs[("ppo_bwd", M)][0]
 b = pol._buffers(M, 0)
 ins = [_ptr(b["obs:" + k]) for k in pol.obs_keys]
 big = torch.empty(1 << 28, dtype=torch.float32, device=DEV)      # 1 GiB

@@ -28,7 +28,8 @@ from typing import Dict, Optional
 import torch as th
 
 from . import _lib, checkpoint, parallel
-from .ppo import INDEX_OBS_KEYS, MlpPolicy, _ptr, obs_width, policy_rows, trainer_obs_keys
+from .checkpoint import trainer_obs_keys
+from .policy import INDEX_OBS_KEYS, MlpPolicy, _ptr, activation_kind, obs_width, policy_rows
 
 
 class EnvStepFunction(th.autograd.Function):
@@ -198,7 +199,6 @@ class BPTT:
 
     def _activations(self, pk):
         """(trunk, extractor) VF_ACTIVATION_* of translated policy_kwargs; refuses what this trainer does not run"""
-        from .ppo import activation_kind
         if pk.get("vf_extractor"):
             raise NotImplementedError(f"{type(self).__name__}: separate pi / vf feature extractors (share_features_extractor=False of the "
                                       "actor-critic policy, pi_features_extractor_class / vf_features_extractor_class) are not implemented: "

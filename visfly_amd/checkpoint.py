@@ -26,6 +26,8 @@ from typing import Dict, List, Optional
 
 import torch as th
 
+from .policy import ACTIVATION_NAMES, INDEX_OBS_KEYS, POLICY_OBS_KEYS, activation_kind
+
 _EXTRACTORS = {"StateExtractor": ("state",), "StateTargetExtractor": ("state", "target"), "StateGateExtractor": ("state", "gate")}
 _HEAD_NAMES = {"mean": "action_net", "value": "value_net"}
 ARCHIVE_VERSION = "2.2.1"       # environment.yml:275 pins stable-baselines3==2.2.1
@@ -64,6 +66,14 @@ def extractor_keys(pk: Optional[dict], obs_keys: List[str]) -> tuple:
         return tuple(dict.fromkeys(k for side in sides for k in side))
     cls = pk.get("features_extractor_class", "StateTargetExtractor" if "target" in obs_keys else "StateExtractor")
     return _EXTRACTORS.get(name(cls), ())
+
+
+def trainer_obs_keys(obs, policy_kwargs):
+    """the observation keys a trainer keeps: "state" and "target" as ever, "gate" only when the extractor the policy_kwargs name reads
+    it (StateGateExtractor / a native `extractor` dict with a "gate" branch)"""
+    avail = [k for k in obs.keys() if k in POLICY_OBS_KEYS]
+    named = extractor_keys(policy_kwargs, avail)
+    return [k for k in avail if k not in INDEX_OBS_KEYS or k in named]
 
 
 def _separate_sides(pk):
@@ -119,7 +129,6 @@ def policy_kwargs_from_reference(pk: Optional[dict], obs_keys: List[str]) -> dic
     # trunks: the policy's activation_fn -- the reference's default is Tanh (policies.py:108; its YAMLs set relu); extractor MLPs:
     # features_extractor_kwargs.activation_fn -- default ReLU (extractors.py:560,583,666).  relu | tanh | elu | leaky_relu
     # (policies.py:64-69) as strings or torch classes
-    from .ppo import activation_kind
     out["activation"] = activation_kind(pk.get("activation_fn", "tanh"))
     out["extractor_activation"] = activation_kind((pk.get("features_extractor_kwargs") or {}).get("activation_fn", "relu"))
     if pk.get("squash_output", True) is False:
@@ -290,15 +299,12 @@ def _param_order(policy):
 
 def activation_spec(policy) -> dict:
     """the (trunk, extractor) activations of a policy under the names MlpPolicy.spec uses, ReLU included"""
-    from .ppo import ACTIVATIONS
-    name = {v: k for k, v in ACTIVATIONS.items()}
-    return dict(activation=name[policy.act], extractor_activation=name[policy.ext_act])
+    return dict(activation=ACTIVATION_NAMES[policy.act], extractor_activation=ACTIVATION_NAMES[policy.ext_act])
 
 
 def check_activations(policy, spec):
     """weights must never run through another nonlinearity than the one they were trained with: ValueError when the activations an
     archive's spec names differ from the policy's.  A spec without the fields (archives written before they existed) is a ReLU network."""
-    from .ppo import activation_kind
     spec = spec if isinstance(spec, dict) else {}
     want = activation_kind(spec.get("activation", "relu")), activation_kind(spec.get("extractor_activation", "relu"))
     if want != (policy.act, policy.ext_act):

@@ -14,7 +14,7 @@ import torch as th
 
 from . import _lib, parallel
 from .envs.base import EP_SUCCESS
-from .ppo import _ptr, policy_rows
+from .policy import _ptr, policy_rows
 
 
 class EvalResult:

@@ -45,7 +45,7 @@ import torch as th
 
 from . import _lib, checkpoint, parallel
 from .bptt import BPTT, LOG_STD_MAX, LOG_STD_MIN
-from .ppo import MlpPolicy, _ptr, policy_rows
+from .policy import MlpPolicy, _ptr, policy_rows
 
 
 class SHAC(BPTT):
