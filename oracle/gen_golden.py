@@ -236,6 +236,14 @@ DYN_CASES = {
                                 integrator="euler"), [0, 0.05, 0, 0], 0.15),
     "dyn_position_euler": (dict(action_type="position", dt=0.0025, ctrl_dt=0.02, ctrl_delay=True,
                                 integrator="euler"), [0.1, 0.1, 0, 0.15], 0.1),
+    # action delay ring at depths other than the default 3 (delay_steps = int(comm_delay / ctrl_dt), dynamics.py): one slot, the
+    # reference's own debug scripts' comm_delay = 0.09 (four slots) and five slots
+    "dyn_thrust_delay1": (dict(action_type="thrust", dt=0.0025, ctrl_dt=0.02, ctrl_delay=True, comm_delay=0.02,
+                               integrator="euler"), [-0.8333] * 4, 0.05),
+    "dyn_bodyrate_rk4_delay4": (dict(action_type="bodyrate", dt=0.0025, ctrl_dt=0.02, ctrl_delay=True, comm_delay=0.09,
+                                     integrator="rk4"), [-1 / 3, 0, 0, 0], 0.3),
+    "dyn_bodyrate_delay5": (dict(action_type="bodyrate", dt=0.0025, ctrl_dt=0.02, ctrl_delay=True, comm_delay=0.1,
+                                 integrator="euler"), [-1 / 3, 0, 0, 0], 0.3),
 }
 
 
@@ -679,6 +687,11 @@ BPTT_CASES = {
     # BASELINE configs[2]'s dynamics: RK4 with per-agent drag coefficients (plant_drag; tape row S + 2), fast agents so that drag matters
     "bptt_nav_rk4_drag": ("nav", dict(ENV_DYN, integrator="rk4", drag_random=0.5), dict(max_episode_steps=1000, target=[12., 0., 3.]),
                           None, None, 12, dict(layout="hoverish", init="nav_branches", drag=0.5, seed=43)),
+    # delay ring at one, four and five slots with re-spawns inside the horizon (the adjoint's episode cut zeroes every slot).  Episodes
+    # longer than the ring: with max_episode_steps <= delay_steps no action ever leaves the ring and the gradient is identically zero
+    "bptt_hover_delay1": ("hover", dict(ENV_DYN, comm_delay=0.02), dict(max_episode_steps=5), [-1 / 3, 0, 0, 0], 0.3, 12),
+    "bptt_hover_rk4_delay4": ("hover", dict(ENV_DYN, integrator="rk4", comm_delay=0.09), dict(max_episode_steps=9), [-1 / 3, 0, 0, 0], 0.3, 20),
+    "bptt_hover_thrust_delay5": ("hover", dict(RACING_DYN, comm_delay=0.1), dict(max_episode_steps=9), [-0.8333] * 4, 0.05, 20),
     # velocity / position action types have no BPTT fixture: the reference's autograd raises on them ("one of the variables
     # needed for gradient computation has been modified by an inplace operation": the per-agent loop of dynamics.py:446-450
     # / 481-488 writes pose_err[:, i] / ang_vel_err[:, i] in place while earlier slices are saved for backward), tried

@@ -20,11 +20,13 @@ def same(a, b, what):
     assert np.array_equal(bits(a), bits(b)), what
 
 
-def make(cls_name, N, seed=7, **kw):
+def make(cls_name, N, seed=7, dyn_extra=None, max_episode_steps=12, **kw):
+    """dyn_extra: further dynamics keywords (tests/test_delay_ring_gpu.py: comm_delay)"""
     import visfly_amd.envs as E
     dyn = dict(DYN, action_type="thrust") if cls_name == "RacingEnv" else dict(DYN)
+    dyn.update(dyn_extra or {})
     env = getattr(E, cls_name)(num_agent_per_scene=N, seed=seed, dynamics_kwargs=dyn, device="cuda:0", tensor_output=True,
-                               max_episode_steps=12, **kw)          # short episodes: auto-resets inside every run
+                               max_episode_steps=max_episode_steps, **kw)          # short episodes: auto-resets inside every run
     env.reset()
     return env
 

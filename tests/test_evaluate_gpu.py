@@ -196,9 +196,14 @@ G3 = {   # case: (env kind, N, model, thrust bias or None, dynamics, generated c
 
 @pytest.mark.parametrize("case", list(G3))
 def test_g3_persistent_launch_equals_the_loop(case):
+    check_persistent_launch_equals_the_loop(case, *G3[case])
+
+
+def check_persistent_launch_equals_the_loop(case, kind, N, name, bias, dyn, generated):
+    """the body of test_g3_persistent_launch_equals_the_loop; tests/test_delay_ring_gpu.py runs it with other delay-ring depths in `dyn`.
+    -> (the model, the loop's result)"""
     from visfly_amd import _lib
     from visfly_amd.evaluate import evaluate_policy
-    kind, N, name, bias, dyn, generated = G3[case]
     model = make_model(name, make_env(kind, N, dyn=dyn, **({"requires_grad": True} if name in ("shac", "bptt_sac", "bptt_sac_tanh") else {})))
     if bias is not None:
         bias_thrust(model.policy, bias)
@@ -221,6 +226,7 @@ def test_g3_persistent_launch_equals_the_loop(case):
     # without the terminal rows: the same episodes
     p2 = evaluate_policy(model, make_env(kind, N, seed=11, dyn=dyn))
     assert p2.path == "persistent" and p2.terminal_state is None and bits_equal(p2.ep_return, loop.ep_return) and torch.equal(p2.flags, loop.flags)
+    return model, loop
 
 
 # ---- G4: needs-reset rule -----------------------------------------------------------------------------------------------------------

@@ -9,7 +9,8 @@ from _golden import GEOMETRIC, RAW_DRIFT_ABS, assert_bits_equal, assert_close_to
 # incl. the velocity / position action types (dynamics.py:414-496): since r03 their fixtures come from the CR-trig reference
 # (sin / cos = fp64 result rounded once) and are held to the bit for all 256 steps, like bodyrate / thrust
 DYN = ["dyn_bodyrate_euler", "dyn_bodyrate_euler_wide", "dyn_thrust_euler", "dyn_bodyrate_nodelay",
-       "dyn_bodyrate_dt005", "dyn_bodyrate_rk4"] + GEOMETRIC
+       "dyn_bodyrate_dt005", "dyn_bodyrate_rk4",
+       "dyn_thrust_delay1", "dyn_bodyrate_rk4_delay4", "dyn_bodyrate_delay5"] + GEOMETRIC      # (delay ring of 1 / 4 / 5 slots)
 
 
 @pytest.mark.parametrize("name", DYN)

@@ -1163,16 +1163,17 @@ def test_persistent_rollout_of_a_generated_class_equals_the_per_step_loop(env_na
     assert _lib.lib().vf_chain_plugin_launches() > n0
 
 
-def _persistent_rollout_vs_loop(env_name, N, dyn, policy_kwargs=None, max_episode_steps=7, n_steps=20):
+def _persistent_rollout_vs_loop(env_name, N, dyn, policy_kwargs=None, max_episode_steps=7, n_steps=20, dyn_extra=None):
     """collect_rollouts as ONE launch (vf_ppo_rollout: 16 / 32 agents per wave for all n_steps, the same rows-per-wave chain
     vf_mlp_forward picks for N rows) leaves the rollout buffer, the TimeLimit list, the episode statistics, the episode
     outputs and the slab of the launch-by-launch loop, bit for bit -- over two consecutive rollouts with a training pass
     between them (Philox counters, delay-ring phase and spawn counters carry over).  r04: also with the RK4 integrator and per-agent
-    drag randomisation re-drawn at every re-spawn (BASELINE configs[2]'s dynamics, utils/maths.py:353-386, dynamics.py:244-267)"""
+    drag randomisation re-drawn at every re-spawn (BASELINE configs[2]'s dynamics, utils/maths.py:353-386, dynamics.py:244-267).
+    `dyn_extra`: further dynamics keywords (tests/test_delay_ring_gpu.py: comm_delay).  -> the two result dicts, persistent first"""
     import visfly_amd.envs as E
     from visfly_amd.ppo import PPO
     from _golden import ENV_DYN
-    dkw = dict(ENV_DYN)
+    dkw = dict(ENV_DYN, **(dyn_extra or {}))
     if dyn.startswith("rk4"):
         dkw["integrator"] = "rk4"
     if dyn.endswith("drag"):
@@ -1220,6 +1221,7 @@ def _persistent_rollout_vs_loop(env_name, N, dyn, policy_kwargs=None, max_episod
     for k in res[0]:
         assert torch.equal(res[0][k], res[1][k]), k
     assert float((res[0]["1:rewards"].abs() > 0).float().mean()) > 0.5
+    return res
 
 
 @pytest.mark.parametrize("n_steps", [1, 2])
