@@ -20,7 +20,6 @@ steps launch by launch in both directions (``rollout_policy`` / ``reverse_policy
 of every recorded step and ``env.backward_step`` hands them to ``vf_env_step_bwd_wind``; on the reference's tape the wind is a constant
 of the step as well (fixtures ``bptt_wind_*``, ``bptt_loop_hover_wind``).
 """
-import ctypes as C
 import os
 import time
 from typing import Dict, Optional
@@ -96,7 +95,18 @@ def _require_differentiable_actions(env, trainer):
                 "\"thrust\" and \"bodyrate\"; train these action types with PPO")
 
 
+def _pth(path):
+    """file name of a plain torch archive (reference actor, SHAC)"""
+    return path if path.endswith(".pth") else path + ".pth"
+
+
 class BPTT:
+    # True: the reference's own actor (two trunks, mu / clamped state-dependent log_std heads) -- set by naming a td_policies policy;
+    # SHAC always uses it.  _critic_arch / _share_extractor: what _make_reference_actor parses for SHAC's critics
+    reference_actor = False
+    _critic_arch = None
+    _share_extractor = False
+
     def __init__(self, env, horizon: int = 32, gamma: float = 0.99, learning_rate: float = 1e-3,
                  max_grad_norm: float = 0.5, weight_decay: float = 0.0, policy_kwargs: Optional[dict] = None,
                  seed: int = 0, betas=(0.9, 0.999), adam_eps: float = 1e-8, policy=None, dump_step: float = 1e4):
@@ -105,9 +115,9 @@ class BPTT:
         if policy is not None and policy not in REFERENCE_ACTOR_POLICIES:
             raise NotImplementedError(f"policy {policy}: one of {REFERENCE_ACTOR_POLICIES} (vector observations) or None")
         _require_differentiable_actions(env, type(self).__name__)
-        # True: the reference's own actor (two trunks, mu / clamped state-dependent log_std heads); SHAC always uses it
-        self.reference_actor = policy is not None or getattr(self, "reference_actor", False)
-        self._eps_override = None            # tests: the exploration noise of the next horizon(s), fed instead of drawn
+        if policy is not None:
+            self.reference_actor = True
+        self._eps_override = None           # tests: the exploration noise of the next horizon(s), fed instead of drawn
         self.env, self.H, self.gamma = env, horizon, gamma
         self.dump_step = dump_step          # learn(eval_env=...): timesteps between two evaluations (BPTT.py:137)
         self.lr, self.max_grad_norm, self.weight_decay, self.betas, self.adam_eps = learning_rate, max_grad_norm, weight_decay, betas, adam_eps
@@ -164,7 +174,6 @@ class BPTT:
         to 512) run layer by layer on the wide linear kernels: no persistent horizon launches for such a network."""
         pk = dict(policy_kwargs or {})
         na = pk.get("net_arch")
-        self._critic_arch = getattr(self, "_critic_arch", None)
         if isinstance(na, dict) and "qf" in na:                       # SB3 get_actor_critic_arch: dict(pi=..., qf=...)
             self._critic_arch = list(na["qf"])
             pk["net_arch"] = dict({k: v for k, v in na.items() if k != "qf"}, pi=list(na["pi"]), vf=list(na["pi"]))    # (flags such as pi_ln stay)
@@ -174,9 +183,7 @@ class BPTT:
             raise NotImplementedError(f"{type(self).__name__}: pi_features_extractor_class / vf_features_extractor_class (separate pi / vf "
                                       "feature extractors of the actor-critic policy) are not implemented for the td policies; PPO runs them")
         self._share_extractor = bool(pk.pop("share_features_extractor", False))
-        if any(k in pk for k in ("features_extractor_class", "net_arch", "features_extractor_kwargs", "activation_fn")):
-            pk.setdefault("activation_fn", "relu")                    # MTDPolicy's default activation IS ReLU (td_policies.py:297)
-        pk.setdefault("activation_fn", "relu")
+        pk.setdefault("activation_fn", "relu")                        # MTDPolicy's default activation IS ReLU (td_policies.py:297)
         pk = checkpoint.policy_kwargs_from_reference(pk, self.obs_keys)
         act, ext_act = self._activations(pk)
         self._extractor = pk.get("extractor", {k: [128, 64] for k in self.obs_keys})
@@ -253,24 +260,14 @@ class BPTT:
         step stay in their slot, the weight gradient is reduced once over the rows of all H steps, and where the library has the
         kernels each half is ONE persistent launch (vf_bptt_rollout / vf_bptt_reverse, actor class (b)) that leaves what the
         launch-by-launch loop below leaves, bit for bit."""
-        env, pol, N, H = self.env, self.policy, self.env.num_envs, self.H
+        env, pol, keys = self.env, self.policy, self.obs_keys
         L, st, dev = _lib.lib(), _lib.current_stream(self.device), self.device
-        keys = self.obs_keys
-        pol.grad.zero_()
-        pol.reserve_slots(N, H)
-        if self._defer_wgrad is None:
-            self._defer_wgrad = pol.backward_data_supported(N, both_heads=True)
-        defer = self._defer_wgrad
+        N, H, defer, disc, loss_vec, eps, t0, scale = self._open_sweep(self.H, two_heads=True)
         f = dict(dtype=th.float32, device=dev)
-        disc, loss_vec = th.ones(N, **f), th.zeros(N, **f)
-        eps = self._eps_override if self._eps_override is not None else self._noise(H, N)
-        assert eps.shape == (H, N, 4)
         acts, drews = th.empty((H, N, 4), **f), th.empty((H, N), **f)
-        ls_rows = pol._slot_blocks[N][1]["value"]                                      # (slots, N, 4): slot t's log_std head
-        t0 = env._tape_t
         fused = False
         if defer and self.fused_rollout:
-            fused = env.rollout_policy(pol, keys, eps, acts, drews, loss_vec, disc, float(self.gamma), 1.0 / (N * self.world))
+            fused = env.rollout_policy(pol, keys, eps, acts, drews, loss_vec, disc, float(self.gamma), scale)
         if fused:
             self._last_rollout = dict(action=acts, done=env._tape_done[t0:t0 + H])
         else:
@@ -284,16 +281,46 @@ class BPTT:
             self._last_rollout["reward"][t].copy_(reward)
             self._last_rollout["done"][t].copy_(done)
             _lib.check(L.vf_bptt_accumulate(_ptr(reward), done.data_ptr(), _ptr(disc), _ptr(loss_vec), _ptr(drews[t]),
-                                            float(self.gamma), 1.0 / (N * self.world), N, st))     # :123-124
+                                            float(self.gamma), scale, N, st))                      # :123-124
+        self._reverse_two_heads(t0, eps, acts, drews, fused)
+        self._horizon = dict(actions=acts, loss_vec=loss_vec)       # per-agent rows of the last horizon (tests, diagnostics)
+        return loss_vec.mean() / self.world
+
+    def _open_sweep(self, noise_rows, two_heads):
+        """what every reverse sweep starts with -> (N, H, defer, disc, loss_vec, eps, t0, scale): policy.grad zeroed, the activation slots
+        of the H steps reserved, the weight gradient deferred to one reduction per horizon where the network has the data-gradient kernel
+        (decided at the first update), discount / loss rows, the exploration noise of the horizon in one draw ((noise_rows, N, 4): H rows,
+        SHAC 2 H; the two-head sweeps take the tests' ``_eps_override`` instead), the tape position of step 0 and the loss scale
+        1 / global agent count"""
+        pol, N, H, dev = self.policy, self.env.num_envs, self.H, self.device
+        pol.grad.zero_()
+        # reference-default policy shapes: the weight gradient is reduced ONCE per horizon over the rows of all H
+        # steps (their activations / masked gradients are stored back to back), the per-step reverse pass is the
+        # register-chained data-gradient kernel only
+        pol.reserve_slots(N, H)          # no-op while the slots exist (they are dropped if many other batch sizes pass through)
+        if self._defer_wgrad is None:
+            self._defer_wgrad = pol.backward_data_supported(N, both_heads=True) if two_heads else pol.backward_data_supported(N)
+        disc, loss_vec = th.ones(N, dtype=th.float32, device=dev), th.zeros(N, dtype=th.float32, device=dev)
+        eps = self._eps_override if two_heads and self._eps_override is not None else self._noise(noise_rows, N)
+        assert eps.shape == (noise_rows, N, 4)
+        return N, H, self._defer_wgrad, disc, loss_vec, eps, self.env._tape_t, 1.0 / (N * self.world)
+
+    def _reverse_two_heads(self, t0, eps_a, actions, drews, fused):
+        """reverse half of a horizon of the reference's actor (BPTT and SHAC), t = H-1 .. 0: adjoint env step -> action head reverse
+        (d mu, d log_std) -> both trunks + extractor -> gradient w.r.t. the observation of step t; ONE persistent launch after a fused
+        forward half (``fused``) where the library has the kernel.  Returns once policy.grad holds the horizon's weight gradient"""
+        env, pol, N, H, defer = self.env, self.policy, self.env.num_envs, self.H, self._defer_wgrad
+        L, st = _lib.lib(), _lib.current_stream(self.device)
+        ls_rows = pol._slot_blocks[N][1]["value"]                                      # (slots, N, 4): slot t's log_std head
         g_obs = None
-        d_mus, d_lss = th.empty((H, N, 4), **f), th.empty((H, N, 4), **f)
+        d_mus, d_lss = th.empty((H, N, 4), device=self.device), th.empty((H, N, 4), device=self.device)
         rev = False
         if fused and self.fused_reverse:
-            rev = env.reverse_policy(pol, H, eps, acts, drews, d_mus, None, d_log_stds=d_lss)
+            rev = env.reverse_policy(pol, H, eps_a, actions, drews, d_mus, None, d_log_stds=d_lss)
         for t in reversed(range(0 if not rev else H, H)):
             d_action = env.backward_step(t0 + t, g_obs, drews[t])
-            _lib.check(L.vf_shac_head_bwd(_ptr(d_action), _ptr(acts[t]), _ptr(ls_rows[t]), _ptr(eps[t]), _ptr(d_mus[t]), _ptr(d_lss[t]), N,
-                                          LOG_STD_MIN, LOG_STD_MAX, st))
+            _lib.check(L.vf_shac_head_bwd(_ptr(d_action), _ptr(actions[t]), _ptr(ls_rows[t]), _ptr(eps_a[t]), _ptr(d_mus[t]),
+                                          _ptr(d_lss[t]), N, LOG_STD_MIN, LOG_STD_MAX, st))
             if defer:
                 d_in = pol.backward_data(d_mus[t], t, d_value=d_lss[t])
             else:
@@ -301,8 +328,6 @@ class BPTT:
             g_obs = d_in.get("state") if t > 0 else None
         if defer:
             pol.weight_grad_slots(N, H, d_mus, accumulate=True, d_value_all=d_lss)
-        self._horizon = dict(actions=acts, loss_vec=loss_vec)       # per-agent rows of the last horizon (tests, diagnostics)
-        return loss_vec.mean() / self.world
 
     def _grad_reverse_sweep(self):
         """explicit reverse sweep: no autograd tape.  Forward: policy (activations of every step stay resident in their
@@ -312,29 +337,19 @@ class BPTT:
         is what step t-1 returned.  dLoss/d reward_t = -disc_t / N is known in the forward pass (:123)."""
         if self.reference_actor:
             return self._grad_reverse_sweep_reference_actor()
-        env, pol, N, H = self.env, self.policy, self.env.num_envs, self.H
+        env, pol = self.env, self.policy
         L, st, dev = _lib.lib(), _lib.current_stream(self.device), self.device
-        pol.grad.zero_()
-        # reference-default policy shapes: the weight gradient is reduced ONCE per horizon over the rows of all H
-        # steps (their activations / masked gradients are stored back to back), the per-step reverse pass is the
-        # register-chained data-gradient kernel only
-        pol.reserve_slots(N, H)          # no-op while the slots exist (they are dropped if many other batch sizes pass through)
-        if self._defer_wgrad is None:
-            self._defer_wgrad = pol.backward_data_supported(N)
-        defer = self._defer_wgrad
-        disc, loss_vec = th.ones(N, device=dev), th.zeros(N, device=dev)
+        N, H, defer, disc, loss_vec, epss, t0, scale = self._open_sweep(self.H, two_heads=False)
         g_ls = th.zeros((N, 4), device=dev)
         log_std = pol.log_std
-        t0 = env._tape_t
         obs = env.get_observation()
-        # per-horizon buffers in one allocation each; the exploration noise of the whole horizon is one draw
+        # per-horizon buffers in one allocation each
         acts, drews = th.empty((H, N, 4), device=dev), th.empty((H, N), device=dev)
-        epss = self._noise(H, N)
         ckpt_done = False
         fused = False
         if defer and self.fused_rollout and pol._act_fused is not False:
             # the whole forward half as one persistent launch (vf_bptt_rollout): same kernels' arithmetic, same buffers
-            fused = env.rollout_policy(pol, self.obs_keys, epss, acts, drews, loss_vec, disc, float(self.gamma), 1.0 / (N * self.world))
+            fused = env.rollout_policy(pol, self.obs_keys, epss, acts, drews, loss_vec, disc, float(self.gamma), scale)
         for t in range(0 if not fused else H, H):
             action = acts[t]
             o = policy_rows(obs, self.obs_keys)
@@ -347,11 +362,11 @@ class BPTT:
             ckpt_done = t + 1 < H and env._tape_t < env._tape.shape[0]
             if ckpt_done:
                 _lib.check(L.vf_bptt_accumulate_checkpoint(_ptr(reward), done.data_ptr(), _ptr(disc), _ptr(loss_vec), _ptr(drews[t]),
-                                                           float(self.gamma), 1.0 / (N * self.world), N, _ptr(env._slab),
+                                                           float(self.gamma), scale, N, _ptr(env._slab),
                                                            _ptr(env._tape[env._tape_t]), env._slab.numel(), st))
             else:
                 _lib.check(L.vf_bptt_accumulate(_ptr(reward), done.data_ptr(), _ptr(disc), _ptr(loss_vec), _ptr(drews[t]),
-                                                float(self.gamma), 1.0 / (N * self.world), N, st))
+                                                float(self.gamma), scale, N, st))
         g_obs = None
         d_means = th.empty((H, N, 4), device=dev)
         g_ls_rows = th.zeros((H, N, 4), device=dev) if defer else None     # log_std gradient terms, one row per (step, agent)
@@ -403,35 +418,27 @@ class BPTT:
     def _apply(self, loss):
         env, pol, N = self.env, self.policy, self.env.num_envs
         parallel.allreduce_sum_(pol.grad)
-        L, st = _lib.lib(), _lib.current_stream(self.device)
         self._opt_step += 1
-        _lib.check(L.vf_sumsq(_ptr(pol.grad), pol.n_params, _ptr(self._sumsq), _ptr(self._scratch), st))
-        pmap, packed = pol.pack_map()
-        cfg = _lib.AdamCfg(self.lr, self.betas[0], self.betas[1], self.adam_eps, self.weight_decay, self.max_grad_norm,
-                           self._opt_step, 0, _ptr(pmap), _ptr(packed))
-        _lib.check(L.vf_adam_step(_ptr(pol.flat), _ptr(pol.grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), pol.n_params,
-                                  _ptr(self._sumsq), C.byref(cfg), st))
-        pol.mark_updated(packed_current=pmap is not None)
-        env.detach()                                          # :134
+        pol.adam_step(self.exp_avg, self.exp_avg_sq, self._sumsq, self._scratch, self.lr, self.betas, self.adam_eps, self.weight_decay,
+                      self.max_grad_norm, self._opt_step)
+        env.detach()                                         # :134
         self.num_timesteps += self.H * N * self.world
         return loss.detach() * self.world
 
     def predict(self, obs, state=None, episode_start=None, deterministic: bool = False):
         """SB3-style predict (utils/evaluate.py:94): -> (action, None); deterministic: a = tanh(mean)"""
         N = obs[self.obs_keys[0]].shape[0]
-        if self.reference_actor:         # shac.py:334-343 / MTDPolicy.predict
-            mu, ls = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1)
-            if deterministic:
-                return th.tanh(mu), None
-            eps = self._noise(1, N)[0]
-            action = th.empty((N, 4), device=self.device)
-            self._head_fwd(mu, ls.contiguous(), eps, action)
-            return action, None
-        mean, _ = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1, need_value=False)
+        # (reference actor -- shac.py:334-343 / MTDPolicy.predict: the second head is the state-dependent log_std)
+        mean, ls = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1,
+                                       need_value=self.reference_actor)
         if deterministic:
             return th.tanh(mean), None
         eps = self._noise(1, N)[0]
-        return th.tanh(mean + self.policy.log_std.exp() * eps), None
+        if not self.reference_actor:
+            return th.tanh(mean + self.policy.log_std.exp() * eps), None
+        action = th.empty((N, 4), device=self.device)
+        self._head_fwd(mean, ls.contiguous(), eps, action)
+        return action, None
 
     # ---- checkpoints ----
     # MlpPolicy actor: the SB3-layout zip of checkpoint.py.  Reference actor (and SHAC): the reference pickles the whole SB3 policy
@@ -443,7 +450,7 @@ class BPTT:
                 "noise_step": int(self._noise_step),
                 "spec": dict(extractor=self._extractor, pi=self.policy.spec["pi"], qf=self._critic_arch, horizon=self.H,
                              gamma=self.gamma, learning_rate=self.lr, algo=type(self).__name__, **checkpoint.activation_spec(self.policy),
-                             share_features_extractor=bool(getattr(self, "_share_extractor", False)))}
+                             share_features_extractor=self._share_extractor)}
 
     def _load_state(self, d, load_optimizer=True):
         checkpoint.check_activations(self.policy, d.get("spec"))
@@ -460,12 +467,12 @@ class BPTT:
     def save(self, path: str):
         if not self.reference_actor:
             return checkpoint.save(self, path)
-        th.save(self._state(), path if path.endswith(".pth") else path + ".pth")
+        th.save(self._state(), _pth(path))
 
     def set_parameters(self, path: str, load_optimizer: bool = True):
         if not self.reference_actor:
             return checkpoint.load_into(self, path, load_optimizer)
-        self._load_state(th.load(path if path.endswith(".pth") else path + ".pth", map_location="cpu"), load_optimizer)
+        self._load_state(th.load(_pth(path), map_location="cpu"), load_optimizer)
         return self
 
     @staticmethod
@@ -481,7 +488,7 @@ class BPTT:
     @classmethod
     def load(cls, path: str, env, **kwargs):
         if path.endswith(".pth") or (not path.endswith(".zip") and os.path.exists(path + ".pth")):
-            d = th.load(path if path.endswith(".pth") else path + ".pth", map_location="cpu")
+            d = th.load(_pth(path), map_location="cpu")
             spec, load_opt = d["spec"], kwargs.pop("load_optimizer", True)
             kwargs.setdefault("policy_kwargs", cls._policy_kwargs_from_spec(spec))
             kwargs.setdefault("horizon", spec["horizon"])

@@ -432,7 +432,7 @@ class MlpPolicy:
         """call after writing ``self.flat`` (optimiser step, load): the packed forward weights are refreshed
         by the next forward.  With ``lazy_pack`` False (default) every forward repacks -- safe for callers that
         write ``flat`` directly; the trainers set ``lazy_pack`` and call this after each step.
-        ``packed_current``: the writer already refreshed the packed images (vf_adam_step with a pack map)."""
+        ``packed_current``: the writer already refreshed the packed images (adam_step below, with a pack map)."""
         self._stamp += 1
         if packed_current and self._packed is not None:
             self._packed_stamp = self._stamp
@@ -462,6 +462,23 @@ class MlpPolicy:
             self._stamp += 1          # force one full pack (zero pads) before the incremental refreshes
             self._pack()
         return self._pack_map, self._packed
+
+    def adam_step(self, exp_avg, exp_avg_sq, sumsq, scratch, lr, betas, eps, weight_decay, max_grad_norm, step,
+                  sumsq_partials=None, sumsq_tail_from=0):
+        """clip ``self.grad`` to ``max_grad_norm`` (None / 0: no clip) and take one Adam step on ``self.flat``; the launch refreshes
+        the packed MFMA weight images as well (pack_map).  The squared gradient norm goes through ``sumsq`` (1 float; ``scratch``: 4096
+        floats of reduction scratch) unless ``sumsq_partials`` = (fp64 device tensor, count) carries it as the per-block partial sums the
+        weight-gradient fold left, to which the launch adds grad[sumsq_tail_from:]^2 (what the fold does not cover: log_std)."""
+        L, st = _lib.lib(), self._stream()
+        if sumsq_partials is None:
+            _lib.check(L.vf_sumsq(_ptr(self.grad), self.n_params, _ptr(sumsq), _ptr(scratch), st))
+        pmap, packed = self.pack_map()
+        part, n_part = (None, 0) if sumsq_partials is None else (sumsq_partials[0].data_ptr(), sumsq_partials[1])
+        cfg = _lib.AdamCfg(lr, betas[0], betas[1], eps, weight_decay, max_grad_norm if max_grad_norm is not None else 0.0, step, 0,
+                           _ptr(pmap), _ptr(packed), part, n_part, sumsq_tail_from)
+        _lib.check(L.vf_adam_step(_ptr(self.flat), _ptr(self.grad), _ptr(exp_avg), _ptr(exp_avg_sq), self.n_params, _ptr(sumsq),
+                                  C.byref(cfg), st))
+        self.mark_updated(packed_current=pmap is not None)
 
     def _pack(self):
         if self._packed is None:

@@ -365,20 +365,10 @@ class PPO:
             if kl > 1.5 * self.target_kl:
                 return None
         self._opt_step += 1
-        if sq is None:
-            _lib.check(L.vf_sumsq(_ptr(pol.grad), pol.n_params, _ptr(self._sumsq), _ptr(self._scratch), st))
-        pmap, packed = pol.pack_map()          # Adam refreshes the packed MFMA weight images in the same launch
-        acfg = self._adam_cfg(self._opt_step, pmap, packed, sq)
-        _lib.check(L.vf_adam_step(_ptr(pol.flat), _ptr(pol.grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), pol.n_params,
-                                  _ptr(self._sumsq), C.byref(acfg), st))
-        pol.mark_updated(packed_current=pmap is not None)
+        # (with the fold's partials `sq` no separate grad-norm launch; Adam adds them and the log_std tail up itself)
+        pol.adam_step(self.exp_avg, self.exp_avg_sq, self._sumsq, self._scratch, self.lr, self.betas, self.adam_eps, self.weight_decay,
+                      self.max_grad_norm, self._opt_step, sumsq_partials=sq, sumsq_tail_from=pol.log_std_off)
         return self._stats
-
-    def _adam_cfg(self, step, pmap, packed, sq):
-        return _lib.AdamCfg(self.lr, self.betas[0], self.betas[1], self.adam_eps, self.weight_decay,
-                            self.max_grad_norm if self.max_grad_norm is not None else 0.0, step, 0,
-                            _ptr(pmap), _ptr(packed), None if sq is None else sq[0].data_ptr(), 0 if sq is None else sq[1],
-                            self.policy.log_std_off)
 
     def train(self, permutations=None):
         """PPO.train (PPO.py:177-337): n_epochs passes over random minibatches (SB3 RolloutBuffer.get: the trailing

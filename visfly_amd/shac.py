@@ -38,13 +38,12 @@ columns into qf0 / qf1) still runs layer by layer.
 
 Under string wind functions the actor's horizon steps launch by launch, forward and reverse (bptt.py; fixture ``shac_hover_wind``).
 """
-import ctypes as C
 from typing import Optional
 
 import torch as th
 
-from . import _lib, checkpoint, parallel
-from .bptt import BPTT, LOG_STD_MAX, LOG_STD_MIN
+from . import _lib, parallel
+from .bptt import BPTT, REFERENCE_ACTOR_POLICIES
 from .policy import MlpPolicy, _ptr, policy_rows
 
 
@@ -55,10 +54,9 @@ class SHAC(BPTT):
                  pre_stop: float = 0.1, policy_noise: float = 0.0, device=None, seed: int = 42, lamda: float = 0.95,
                  max_grad_norm: float = 0.5, **kw):
         # argument list of TemporalDifferBase.__init__ (shac.py:50-72); buffer_size / batch_size / clip_range_vf / pre_stop /
-        # policy_noise are stored but unused by the reference's loop as well
-        if policy not in (None, "MultiInputPolicy", "MlpPolicy", "MTDPolicy"):
+        # policy_noise are stored but unused by the reference's loop as well.  The policy names are BPTT's, less "CnnPolicy"
+        if policy is not None and (policy not in REFERENCE_ACTOR_POLICIES or policy == "CnnPolicy"):
             raise NotImplementedError(f"policy {policy}: vector-observation MTDPolicy only")
-        self._critic_arch = None
         self.tau, self.gradient_steps, self.lamda = tau, gradient_steps, lamda
         self.fused_critic = True       # a critic update's per-row part as one launch (vf_twin_q_update); False: the three-launch step (tests)
         kw.pop("policy", None)
@@ -73,7 +71,6 @@ class SHAC(BPTT):
         # share_features_extractor=True (td_policies.py:127; SB3 SACPolicy._build): critic.features_extractor IS the actor's -- run under
         # no_grad, left alone by the critic's optimiser; the TARGET keeps its own copy (initialised from it, Polyak-averaged with the rest).
         # Here: the critic's extractor block of `flat` mirrors the actor's (same layer order and offsets: extractor layers lead both tables)
-        self._share_extractor = bool(getattr(self, "_share_extractor", False))
         self._ext_end = sum(ly.K * ly.No + ly.No for ly in self._ext_layers()) if self._share_extractor else 0
         self._stale_ext = th.zeros(self._ext_end, device=dev) if self._share_extractor else None
         if self._share_extractor:
@@ -120,35 +117,25 @@ class SHAC(BPTT):
 
     # ---- actor: horizon roll-out + reverse sweep ------------------------------------------------------------------------------
     def _grad_reverse_sweep(self):
-        """shac.py:215-266 forward, then the reverse sweep t = H-1 .. 0: adjoint env step -> action head -> both actor trunks ->
-        gradient w.r.t. the observation of step t, which step t-1 returned.  Like BPTT's reference-actor sweep the activations of
+        """shac.py:215-266 forward, then the reverse sweep (BPTT._reverse_two_heads) t = H-1 .. 0: adjoint env step -> action head -> both
+        actor trunks -> gradient w.r.t. the observation of step t, which step t-1 returned.  Like BPTT's reference-actor sweep the activations of
         every step stay in their slot and the actor's weight gradient is reduced once over the H N rows of the horizon.  Where the
         library has the kernels (vf_bptt_rollout / vf_bptt_reverse, actor class (b)) the closed loop policy -> env -> policy and its
         reverse are ONE persistent launch each; the terms of the loss VALUE that are constants of the actor objective -- next action
         and target critics on the detached next observation (:234-239) -- follow over the recorded horizon: the next observation of
         step t IS the input of slot t + 1, so its actor heads are already there (same weights), only the last step's are computed.
         Leaves what the launch-by-launch loop leaves, bit for bit (tests/test_shac_gpu.py)."""
-        env, pol, N, H = self.env, self.policy, self.env.num_envs, self.H
+        env, pol, keys = self.env, self.policy, self.obs_keys
         L, st, dev = _lib.lib(), _lib.current_stream(self.device), self.device
-        keys = self.obs_keys
-        pol.grad.zero_()
-        pol.reserve_slots(N, H)
-        if self._defer_wgrad is None:
-            self._defer_wgrad = pol.backward_data_supported(N, both_heads=True)
-        defer = self._defer_wgrad
+        N, H, defer, disc, loss_vec, eps, t0, scale = self._open_sweep(2 * self.H, two_heads=True)
         blk = pol._slot_blocks[N][1]
-        disc, loss_vec = th.ones(N, device=dev), th.zeros(N, device=dev)
         f = dict(dtype=th.float32, device=dev)
         u8 = dict(dtype=th.uint8, device=dev)
         b = self._buf = dict(obs={k: th.empty((H, N, pol.obs_dims[k]), **f) for k in keys}, action=th.empty((H, N, 4), **f),
                              reward=th.empty((H, N), **f), done=th.empty((H, N), **u8), ep_done=th.empty((H, N), **u8),
                              next_value=th.empty((H, N), **f))
-        eps = self._eps_override if self._eps_override is not None else self._noise(2 * H, N)
-        assert eps.shape == (2 * H, N, 4)
         eps_a = eps[0::2].contiguous()                                                 # [t] = noise of the action of step t
-        drews, ls_rows = th.empty((H, N), **f), blk["value"]
-        scale = 1.0 / (N * self.world)
-        t0 = env._tape_t
+        drews = th.empty((H, N), **f)
         fused = False
         if defer and self.fused_rollout:
             flag_rows = th.empty((H, N), **u8)
@@ -209,22 +196,7 @@ class SHAC(BPTT):
             _lib.check(L.vf_shac_accumulate(_ptr(reward), done.data_ptr(), env._ep_flags.data_ptr(), _ptr(q0), _ptr(q1), _ptr(disc),
                                             _ptr(loss_vec), _ptr(drews[t]), _ptr(b["next_value"][t]), b["ep_done"][t].data_ptr(),
                                             float(self.gamma), scale, 1 if t == H - 1 else 0, N, st))
-        g_obs = None
-        d_mus, d_lss = th.empty((H, N, 4), **f), th.empty((H, N, 4), **f)
-        rev = False
-        if fused and self.fused_reverse:
-            rev = env.reverse_policy(pol, H, eps_a, b["action"], drews, d_mus, None, d_log_stds=d_lss)
-        for t in reversed(range(0 if not rev else H, H)):
-            d_action = env.backward_step(t0 + t, g_obs, drews[t])
-            _lib.check(L.vf_shac_head_bwd(_ptr(d_action), _ptr(b["action"][t]), _ptr(ls_rows[t]), _ptr(eps_a[t]), _ptr(d_mus[t]),
-                                          _ptr(d_lss[t]), N, LOG_STD_MIN, LOG_STD_MAX, st))
-            if defer:
-                d_in = pol.backward_data(d_mus[t], t, d_value=d_lss[t])
-            else:
-                d_in = pol.backward(d_mus[t], d_lss[t], None, accumulate=True, need_input_grad=t > 0, slot=t)
-            g_obs = d_in.get("state") if t > 0 else None
-        if defer:
-            pol.weight_grad_slots(N, H, d_mus, accumulate=True, d_value_all=d_lss)
+        self._reverse_two_heads(t0, eps_a, b["action"], drews, fused)
         self._horizon = dict(actions=b["action"], rewards=b["reward"], loss_vec=loss_vec)   # per-agent rows of the last horizon
         return loss_vec.mean() / self.world
 
@@ -279,14 +251,9 @@ class SHAC(BPTT):
         if self._share_extractor:          # no gradient reaches the shared extractor from the critic loss; what its .grad holds is the actor's (above)
             c.grad[:self._ext_end].copy_(self._stale_ext)
         self._last_critic_grad = c.grad
-        _lib.check(L.vf_sumsq(_ptr(c.grad), c.n_params, _ptr(self._c_sumsq), _ptr(self._scratch), st))
         self._critic_step += 1
-        pmap, packed = c.pack_map()
-        cfg = _lib.AdamCfg(self.lr, self.betas[0], self.betas[1], self.adam_eps, 0.0, self.max_grad_norm, self._critic_step, 0,
-                           _ptr(pmap), _ptr(packed))
-        _lib.check(L.vf_adam_step(_ptr(c.flat), _ptr(c.grad), _ptr(self.c_exp_avg), _ptr(self.c_exp_avg_sq), c.n_params,
-                                  _ptr(self._c_sumsq), C.byref(cfg), st))
-        c.mark_updated(packed_current=pmap is not None)
+        c.adam_step(self.c_exp_avg, self.c_exp_avg_sq, self._c_sumsq, self._scratch, self.lr, self.betas, self.adam_eps, 0.0,
+                    self.max_grad_norm, self._critic_step)
         if self._share_extractor:
             # the critic's optimiser does not own the extractor: its parameters stay the actor's, its moments never existed; the clip
             # rescaled the stale gradient in place
@@ -306,18 +273,7 @@ class SHAC(BPTT):
             loss = self._critic_step_once(obs, action, target)
         return loss
 
-    # ---- inference -------------------------------------------------------------------------------------------------------------
-    def predict(self, obs, state=None, episode_start=None, deterministic: bool = False):
-        """shac.py:334-343 / MTDPolicy.predict: -> (action, None); deterministic: tanh(mu)"""
-        N = obs[self.obs_keys[0]].shape[0]
-        mu, ls = self.policy.forward(policy_rows(obs, self.obs_keys), save_activations=False, slot=self.H + 1)
-        if deterministic:
-            return th.tanh(mu), None
-        eps = self._noise(1, N)[0]
-        action = th.empty((N, 4), device=self.device)
-        self._head_fwd(mu, ls.contiguous(), eps, action)
-        return action, None
-
+    # ---- inference: BPTT.predict (the reference's actor) ---- checkpoints ------------------------------------------------------
     def _state(self):
         d = super()._state()
         d.update({"critic": self.critic.flat.cpu(), "critic_target": self.critic_target.flat.cpu(), "c_exp_avg": self.c_exp_avg.cpu(),
