@@ -307,6 +307,38 @@ vf_dyn* vf_env_dyn(vf_env* h);   /* embedded dynamics handle sharing the slab (D
 int vf_env_set_agent_offset(vf_env* h, int64_t first_agent);
 int64_t vf_env_agent_offset(const vf_env* h);   /* the value set, 0 by default; -1 for a null handle */
 
+/* Analytic obstacles (additive within ABI 11).  A handle carries a table of at most VF_MAX_OBSTACLES solids, shared by all its agents like
+ * the room box; the closest-scene-point query of update_collision (droneEnv.py:345-367) then runs over the room box AND the table.
+ * fp32, every operation rounded on its own (no FMA), IEEE sqrt and division; p = the agent's position, g = the candidate's distance:
+ *   VF_OBST_SPHERE  a = centre c, r = radius:   dx = p - c, d = sqrt((dx0 dx0 + dx1 dx1) + dx2 dx2), g = max(d - r, 0),
+ *                                               cp = p if d <= r else c + dx * (r / d)   (the quotient formed once)
+ *   VF_OBST_BOX     a = lo, b = hi:             q = min(max(p, lo), hi), e = p - q, g = sqrt((e0 e0 + e1 e1) + e2 e2), cp = q
+ *   VF_OBST_PILLAR  a = (cx, cy, z_lo), b[2] = z_hi, r = radius (a vertical cylinder):
+ *                                               dx = p0 - cx, dy = p1 - cy, dxy = sqrt(dx dx + dy dy), er = max(dxy - r, 0),
+ *                                               zc = min(max(p2, z_lo), z_hi), ez = p2 - zc, g = sqrt(er er + ez ez),
+ *                                               s = dxy > r ? r / dxy : 1, cp = (cx + dx s, cy + dy s, zc)
+ * Every primitive is a solid: inside it cp = p.  Candidate 0 is the room box (cp of the bounding-box query, g over v = cp - p in the
+ * plain form above); the smallest g wins, ties go to the first of box, obstacle 0, 1, ...  From the winner's cp: collision_vector =
+ * cp - p, collision_dis = its norm, is_collision = dis < uav_radius, exactly as for an external scene point (vf_env_finish_step);
+ * out-of-bounds stays the room box's test.  The navigation adjoint treats cp as a constant of the step (collision_point.detach()).
+ * Followed by vf_env_step, vf_env_step_n, vf_env_graph_*, vf_env_reset, vf_env_query, vf_env_step_bwd(_wind) and vf_env_finish_step (an
+ * external point, where given, still wins).  While the table is non-empty vf_env_rollout_fused, vf_ppo_rollout, vf_bptt_rollout,
+ * vf_bptt_reverse and vf_eval_rollout return VF_EUNSUPPORTED before any launch.
+ * vf_env_set_obstacles: host_table = n entries (n = 0 clears the table; host_table may then be NULL); VF_EINVAL for n < 0, n >
+ * VF_MAX_OBSTACLES, an unknown type, a non-finite value, r <= 0 (sphere, pillar) or lo >= hi in any component (box; pillar: z_lo >= z_hi).
+ * Rewrites the handle's device constant block after a device-wide synchronisation; a captured vf_env_graph keeps the kernels it was
+ * captured with, so capture after the table is set. */
+#define VF_MAX_OBSTACLES 16
+enum { VF_OBST_SPHERE = 0, VF_OBST_BOX = 1, VF_OBST_PILLAR = 2 };
+typedef struct vf_obstacle {
+    int32_t type;   /* VF_OBST_* */
+    float a[3];
+    float b[3];
+    float r;
+} vf_obstacle;
+int vf_env_set_obstacles(vf_env* h, const vf_obstacle* host_table, int32_t n);
+int32_t vf_env_obstacle_count(const vf_env* h);   /* entries of the table; -1 for a null handle */
+
 /* Time-varying / per-agent wind (envs/base/dynamics.py:132-174,384-388: wind_settings given as strings are eval'ed into
  * functions of (t, previous wind) and re-evaluated by update_wind() at the top of every step; the value then holds for the
  * whole control interval and enters p' = v + wind and the velocity observation, :751-752).  The functions themselves are host
@@ -387,6 +419,12 @@ int vf_env_finish_step(vf_env* h, const float* ext_collision_point, const uint8_
                        int32_t auto_reset, vf_stream_t stream);
 
 int vf_env_query(vf_env* h, const vf_env_view* view, vf_stream_t stream);
+/* The same view after a vf_env_finish_step that was given an external closest point (additive within ABI 11): for every agent i with
+ * skip[i] == 0 (skip NULL: every agent) col_point is ext_collision_point[i] and col_vec / col_dis are formed from it by the arithmetic of
+ * the step kernel itself (vec = point - p, the FMA-chained norm), so that the view reports, bit for bit, the distance the step compared
+ * with uav_radius; the other agents (the ones that re-spawned in the step: pass its done flags) keep this library's own query.
+ * ext_collision_point NULL is vf_env_query. */
+int vf_env_query_ext(vf_env* h, const vf_env_view* view, const float* ext_collision_point, const uint8_t* skip, vf_stream_t stream);
 
 /* RacingEnv2's observation (envs/RacingEnv.py:218-267) from the step kernel's raw state rows: state (N, 3 n_next + 10) =
  * [(gates[(g + k) % n_gates] - p) / radius for k < n_next, q, v / 10, w / 10], gate_out (N,) = g (may be NULL).  Which index g the

@@ -97,6 +97,15 @@ class EnvCfg(C.Structure):
     ]
 
 
+MAX_OBSTACLES = 16        # VF_MAX_OBSTACLES
+OBST_SPHERE, OBST_BOX, OBST_PILLAR = 0, 1, 2
+
+
+class Obstacle(C.Structure):
+    """mirror of vf_obstacle"""
+    _fields_ = [("type", C.c_int32), ("a", C.c_float * 3), ("b", C.c_float * 3), ("r", C.c_float)]
+
+
 class EnvOut(C.Structure):
     """mirror of vf_env_out (device pointers)"""
     _fields_ = [(n, C.c_void_p) for n in ("obs", "reward", "done", "ep_return", "ep_length", "ep_flags",
@@ -255,6 +264,7 @@ SIGNATURES = {
     "vf_dyn_set_wind": (C.c_int, [_vp, _vp]),
     "vf_env_finish_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(EnvOut), C.c_int32, _vp]),
     "vf_env_query": (C.c_int, [_vp, C.POINTER(EnvView), _vp]),
+    "vf_env_query_ext": (C.c_int, [_vp, C.POINTER(EnvView), _vp, _vp, _vp]),
     "vf_env_time_steps": (C.c_int, [_vp, _vp, C.POINTER(EnvOut), C.c_int32, C.c_int32, _vp, C.POINTER(C.c_float)]),
     "vf_env_step_bwd": (C.c_int, [_vp, C.POINTER(EnvBwdArgs), _vp]),
     "vf_env_step_bwd_wind": (C.c_int, [_vp, C.POINTER(EnvBwdArgs), _vp, _vp]),
@@ -309,6 +319,8 @@ SIGNATURES = {
     "vf_noise_fill": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
     "vf_env_set_agent_offset": (C.c_int, [_vp, C.c_int64]),
     "vf_env_agent_offset": (C.c_int64, [_vp]),
+    "vf_env_set_obstacles": (C.c_int, [_vp, C.POINTER(Obstacle), C.c_int32]),
+    "vf_env_obstacle_count": (C.c_int32, [_vp]),
     "vf_ppo_loss": (C.c_int, [_vp] * 10 + [C.c_int32, C.POINTER(PpoLossCfg), _vp, _vp]),
     "vf_gather_rows": (C.c_int, [C.POINTER(GatherFields), _vp, C.c_int64, _vp]),
     "vf_rollout_post": (C.c_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, C.c_int32, _vp]),

@@ -57,6 +57,7 @@ extern "C" int vf_bptt_reverse(vf_env* h, const vf_mlp_bwd_desc* desc, const flo
         misaligned(adj_slab) || (tape_stride & 3))
         return vf::fail(VF_EINVAL, "vf_bptt_reverse: actions / d_action / eps / g_log_std / log_std_rows / tape / adj_slab must be 16-byte aligned (float4 rows)");
     if (h->dyn.wind) return vf::fail(VF_EUNSUPPORTED, "vf_bptt_reverse: per-agent wind rows are set");
+    if (h->n_obst > 0) return vf::fail(VF_EUNSUPPORTED, "vf_bptt_reverse: the handle has an obstacle table (vf_env_set_obstacles): step launch by launch");
     const int S = h->dyn.cfg.interval_steps;
     if (S > 10) return vf::fail(VF_EUNSUPPORTED, "vf_bptt_reverse: at most 10 sub-steps per control interval");
     const int N = h->dyn.N;

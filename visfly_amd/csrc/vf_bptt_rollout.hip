@@ -64,6 +64,7 @@ extern "C" int vf_bptt_rollout(vf_env* h, const vf_mlp_desc* desc, const float* 
     if (!out->reward) return vf::fail(VF_EINVAL, "vf_bptt_rollout: out->reward (N floats of scratch) is required");
     if (!h->dyn.S) return vf::fail(VF_ESTATE, "vf_bptt_rollout: vf_env_bind has not been called");
     if (h->dyn.wind) return vf::fail(VF_EUNSUPPORTED, "vf_bptt_rollout: per-agent wind rows are set");
+    if (h->n_obst > 0) return vf::fail(VF_EUNSUPPORTED, "vf_bptt_rollout: the handle has an obstacle table (vf_env_set_obstacles): step launch by launch");
     if (tape_stride < (int64_t)h->dyn.Npad * h->dyn.G * 4) return vf::fail(VF_EINVAL, "vf_bptt_rollout: tape rows are shorter than the slab");
     if (reinterpret_cast<uintptr_t>(substep_tape) & 15) return vf::fail(VF_EINVAL, "vf_bptt_rollout: substep_tape must be 16-byte aligned");
     if ((int64_t)H * h->dyn.N * 128 * 4 >= (1ll << 32))      // the chain addresses its activation copies with 32-bit byte offsets

@@ -69,11 +69,21 @@ struct vf_env_dev {
     float hit_y;       // hit_threshold(cfg.uav_radius) (vf_step_consts.hpp): `y < hit_y` is `sqrtf(y) < uav_radius` for every y
 };
 
+// ... and behind it the handle's obstacle table (vf_env_set_obstacles).  A block of its own type around vf_env_dev, so that nothing that is
+// sized by vf_env_dev changes; the env handles allocate this one (upload_env_dev), env_scene reads the tail
+struct vf_env_scene {
+    vf_env_dev dev;
+    int n_obst;        // entries of obst in use, 0 = the bare room box
+    int pad[3];
+    vf_obstacle obst[VF_MAX_OBSTACLES];
+};
+
 #ifdef __HIPCC__
 // `e` must be the handle's device block (what the step / roll-out kernels get through their pointer argument), NOT a by-value copy
 // of a vf_env_cfg: k_env_reset takes the value in its argument struct instead
 __device__ __forceinline__ unsigned env_agent0(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_dev&>(e).agent0; }
 __device__ __forceinline__ float env_hit_y(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_dev&>(e).hit_y; }
+__device__ __forceinline__ const vf_env_scene& env_scene(const vf_env_cfg& e) { return reinterpret_cast<const vf_env_scene&>(e); }
 
 // ---- wave64 reductions: fixed shuffle tree, the sum lands in lane 0 ----
 __device__ __forceinline__ double wave_sum(double x)

@@ -7,6 +7,8 @@
 // envs/HoverEnv.py, envs/NavigationEnv.py, envs/RacingEnv.py).  One thread per agent; the
 // env counters ride in the spare components of the dynamics granules, so the env step
 // moves the same bytes as the bare dynamics step plus its outputs.
+#include <cmath>
+
 #include "vf_env_epilogue.hpp"
 
 #pragma clang fp contract(off)
@@ -47,7 +49,9 @@ namespace vf {
 // the loads behind its untaken arm; the arithmetic is the same code.  What depends on data, on N or on a pointer's alignment stays:
 // the episode-end block, the re-spawn, the optional episode outputs behind `if (done)`, the partial / unaligned store path, the delay
 // ring (delay_steps is a preloaded scalar) and is_collision_reset.  profiles/env_straight_line.txt
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool LAZY_SLOT = false, bool STRAIGHT = false>
+//
+// OBST: the handle's obstacle table is not empty (env_epilogue; general instances only, picked by pick_env_kernel for every agent count)
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool LAZY_SLOT = false, bool STRAIGHT = false, bool OBST = false>
 __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, float* S,
                                                      const float4* action, int N, int G, int head, int helper, int delay_steps,
                                                      int g_drag, const EnvArgs g0)
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
 #endif
     const int wave = threadIdx.x >> 6;
 #ifdef VF_ENV_TRACE
-    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13, nullptr, nullptr, tr);
+    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13, nullptr, nullptr, tr);
     asm volatile("" ::: "memory");
     VF_TR(11);                                       // stores issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
         }
     }
 #else
-    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
+    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
 #endif
 }
 
@@ -166,7 +170,8 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
 // The part of the step that follows the dynamics interval, as a launch of its own (vf_env_finish_step): the dynamics ran
 // in vf_dyn_step on the same slab, an external scene manager then answered the collision query for the new poses
 // (droneEnv.py:374-379 with visual=True).  With ext_point = ext_oob = null the two launches equal one vf_env_step bit for bit.
-template <int KIND>
+// OBST: the handle has an obstacle table: where ext_point is null the table is queried instead of the bare box (and for every re-spawn)
+template <int KIND, bool OBST = false>
 __global__ __launch_bounds__(kBlock) void k_env_finish(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, const EnvArgs g)
 {
     const vf_dyn_cfg& c = *cp;
@@ -179,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void k_env_finish(const vf_dyn_cfg* __restr
     load_agent<false>(g.d.S, g.d.G, i, s, sp);
     load_wind(c, g.d, i, live, s);
     const int wave = threadIdx.x >> 6;
-    env_epilogue<KIND, true, 1, true>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
+    env_epilogue<KIND, true, 1, true, false, 0, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
 }
 
 // K consecutive steps in one launch: see vf_env_rollout_fused (include/visfly_amd.h)
@@ -257,8 +262,9 @@ struct EnvResetArgs {
     unsigned agent0;  // vf_env::agent0 (the cfg arrives by value here: no vf_env_dev tail to read it from)
 };
 
+// ep: the handle's device block, read for the obstacle table behind the cfg (scene_collision; an empty table is the box query)
 template <int KIND>
-__global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const vf_env_cfg e, const EnvResetArgs r)
+__global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const vf_env_cfg e, const EnvResetArgs r, const vf_env_cfg* __restrict__ ep)
 {
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= r.k) return;
@@ -284,7 +290,7 @@ __global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const 
         spawn_agent(e, r.agent0, i, episode, r.idx != nullptr, s);
     }
     for (int q = 0; q < c.delay_steps; ++q) *granule(r.d.S, r.d.G, i, VF_G_RING + q) = make_float4(0.f, 0.f, 0.f, 0.f);
-    const Collision col = bbox_collision(e, s.p);
+    const Collision col = scene_collision(*ep, s.p);
     er.flags = (int)(episode << 8);
     er.flags = set_flag(er.flags, VF_F_COLLISION, col.hit);
     er.flags = set_flag(er.flags, VF_F_OUT_BOUNDS, col.oob);
@@ -323,8 +329,9 @@ __global__ __launch_bounds__(kBlock) void k_spawn_tags_clear(float* S, int G, in
     granule(S, G, i, g_spawn + 4)->x = 0.0f;
 }
 
-__global__ __launch_bounds__(kBlock) void k_env_query(const vf_dyn_cfg c, const vf_env_cfg e, const DynArgs d, int g_race,
-                                                      const vf_env_view v)
+// ext / skip: vf_env_query_ext -- the external scene point of the agents with skip[i] == 0, by the EXT arithmetic of env_epilogue
+__global__ __launch_bounds__(kBlock) void k_env_query(const vf_dyn_cfg c, const vf_env_cfg* __restrict__ ep, const DynArgs d, int g_race,
+                                                      const vf_env_view v, const float* __restrict__ ext, const unsigned char* __restrict__ skip)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= d.N) return;
@@ -332,7 +339,13 @@ __global__ __launch_bounds__(kBlock) void k_env_query(const vf_dyn_cfg c, const 
     Spares sp;
     load_agent(d.S, d.G, i, s, sp);
     const EnvRegs er = unpack_env(sp);
-    const Collision col = bbox_collision(e, s.p);
+    Collision col = scene_collision(*ep, s.p);   // the handle's device block: room box + obstacle table
+    if (ext && !(skip && skip[i])) {
+        const float* q = ext + 3 * (size_t)i;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { col.cp[k] = q[k]; col.vec[k] = q[k] - s.p[k]; }
+        col.dis = norm3(col.vec[0], col.vec[1], col.vec[2]);
+    }
     if (v.step_count) v.step_count[i] = er.step_count;
     if (v.rewards) v.rewards[i] = er.rewards;
     if (v.flags) v.flags[i] = (uint8_t)(er.flags & 0xff);
@@ -384,33 +397,34 @@ namespace {
 using EnvKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::EnvArgs);
 using EnvStepKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, float*, const float4*, int, int, int, int, int, int, const vf::EnvArgs);
 
-template <int KIND, int ACT, bool LAZY>
+// OBST: the instances that query the handle's obstacle table (k_env_step)
+template <int KIND, int ACT, bool LAZY, bool OBST>
 EnvStepKernel pick_env_kernel_ka(const vf_dyn_cfg& c)
 {
     const int key = (c.integrator == VF_INT_RK4 ? 2 : 0) | (c.ctrl_delay ? 1 : 0);
     switch (key) {
-    case 0: return vf::k_env_step<KIND, ACT, VF_INT_EULER, false, LAZY>;
-    case 1: return vf::k_env_step<KIND, ACT, VF_INT_EULER, true, LAZY>;
-    case 2: return vf::k_env_step<KIND, ACT, VF_INT_RK4, false, LAZY>;
-    default: return vf::k_env_step<KIND, ACT, VF_INT_RK4, true, LAZY>;
+    case 0: return vf::k_env_step<KIND, ACT, VF_INT_EULER, false, LAZY, false, OBST>;
+    case 1: return vf::k_env_step<KIND, ACT, VF_INT_EULER, true, LAZY, false, OBST>;
+    case 2: return vf::k_env_step<KIND, ACT, VF_INT_RK4, false, LAZY, false, OBST>;
+    default: return vf::k_env_step<KIND, ACT, VF_INT_RK4, true, LAZY, false, OBST>;
     }
 }
 
-template <int KIND, bool LAZY>
+template <int KIND, bool LAZY, bool OBST>
 EnvStepKernel pick_env_kernel_kl(const vf_dyn_cfg& c)
 {
     switch (c.action_type) {
-    case VF_ACT_THRUST: return pick_env_kernel_ka<KIND, VF_ACT_THRUST, LAZY>(c);
-    case VF_ACT_BODYRATE: return pick_env_kernel_ka<KIND, VF_ACT_BODYRATE, LAZY>(c);
-    case VF_ACT_VELOCITY: return pick_env_kernel_ka<KIND, VF_ACT_VELOCITY, LAZY>(c);
-    default: return pick_env_kernel_ka<KIND, VF_ACT_POSITION, LAZY>(c);
+    case VF_ACT_THRUST: return pick_env_kernel_ka<KIND, VF_ACT_THRUST, LAZY, OBST>(c);
+    case VF_ACT_BODYRATE: return pick_env_kernel_ka<KIND, VF_ACT_BODYRATE, LAZY, OBST>(c);
+    case VF_ACT_VELOCITY: return pick_env_kernel_ka<KIND, VF_ACT_VELOCITY, LAZY, OBST>(c);
+    default: return pick_env_kernel_ka<KIND, VF_ACT_POSITION, LAZY, OBST>(c);
     }
 }
 
-template <int KIND>
+template <int KIND, bool OBST = false>
 EnvStepKernel pick_env_kernel_k(const vf_dyn_cfg& c, bool lazy)
 {
-    return lazy ? pick_env_kernel_kl<KIND, true>(c) : pick_env_kernel_kl<KIND, false>(c);
+    return lazy ? pick_env_kernel_kl<KIND, true, OBST>(c) : pick_env_kernel_kl<KIND, false, OBST>(c);
 }
 
 template <int KIND, int ACT>
@@ -491,6 +505,13 @@ EnvStepKernel pick_env_straight_k(const vf_dyn_cfg& c)
 EnvStepKernel pick_env_kernel(const vf_env* h, const vf::EnvArgs& g)
 {
     const bool lazy = h->dyn.Npad > 2 * 65536;          // more than two waves per SIMD (k_env_step, LAZY_SLOT)
+    if (h->n_obst > 0) {                                // an obstacle table: the general kernel's OBST instances, never STRAIGHT
+        switch (h->cfg.kind) {
+        case VF_ENV_HOVER: return pick_env_kernel_k<VF_ENV_HOVER, true>(h->dyn.cfg, lazy);
+        case VF_ENV_NAV: return pick_env_kernel_k<VF_ENV_NAV, true>(h->dyn.cfg, lazy);
+        default: return pick_env_kernel_k<VF_ENV_RACING, true>(h->dyn.cfg, lazy);
+        }
+    }
     const bool straight = !lazy && g.d.g_drag < 0 && !g.d.wind && !g.out.done_list && !g.out.done_count && !g.stale && g.auto_reset &&
                           g.g_spawn_rd >= 0 && g.helper > 0 && h->cfg.obs_mode == VF_OBS_STATE && h->dyn.cfg.action_type == VF_ACT_BODYRATE;
     if (straight && h->cfg.kind == VF_ENV_HOVER) return pick_env_straight_k<VF_ENV_HOVER>(h->dyn.cfg);
@@ -512,7 +533,8 @@ vf::DynArgs dyn_args(const vf_env* h, const float* action, float* obs, int ahead
 int launch_env_step(vf_env* h, const float* action, const vf_env_out* out, int auto_reset, hipStream_t st, int ahead = 0)
 {
     vf::EnvArgs g{dyn_args(h, action, out->obs, ahead), *out, h->g_race, auto_reset};
-    if (vf::use_split(h->dyn.Npad, h->dyn.cfg)) {
+    // (an obstacle table: the one-thread-per-agent kernel at every agent count -- the two-wave split has no OBST instances)
+    if (h->n_obst == 0 && vf::use_split(h->dyn.Npad, h->dyn.cfg)) {
         hipLaunchKernelGGL(pick_env_split(h), dim3(h->dyn.Npad / 128), dim3(vf::kBlock), 0, st, h->dyn.d_cfg, h->d_cfg, g.d.S, g.d.action, g.d.N, g.d.G,
                            g.d.head, 0, h->dyn.cfg.delay_steps, g.d.g_drag, g);
         h->stale_all = 1;
@@ -574,7 +596,7 @@ int vf_env_create(const vf_dyn_cfg* dyn, const vf_env_cfg* env, int32_t N, int32
     h->g_race = racing ? h->dyn.g_extra : -1;
     h->g_spawn = env->spawn_prefetch ? h->dyn.g_extra + racing : -1;
     int rc = vf::upload_dyn_dev(h->dyn.cfg, &h->dyn.d_cfg);
-    if (rc == VF_OK) rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg);
+    if (rc == VF_OK) rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg, h->obst, h->n_obst);
     if (rc == VF_OK && h->g_spawn >= 0 &&
         hipMalloc(reinterpret_cast<void**>(&h->d_stale), (size_t)2 * (h->dyn.Npad / 64) * sizeof(unsigned long long)) != hipSuccess) {
         h->d_stale = nullptr;            // no bits: the helper compares every tag, as before
@@ -609,7 +631,7 @@ int vf_env_set_agent_offset(vf_env* h, int64_t first_agent)
     // hipMemcpy from pageable memory returns after the copy and is ordered behind the null stream's work only: a launch of this
     // handle still in flight on another stream must not see the block change under it
     VF_HIP(hipDeviceSynchronize());
-    if (int rc = vf::upload_env_dev(h->cfg, (unsigned)first_agent, &h->d_cfg)) return rc;
+    if (int rc = vf::upload_env_dev(h->cfg, (unsigned)first_agent, &h->d_cfg, h->obst, h->n_obst)) return rc;
     h->agent0 = (unsigned)first_agent;
     if (h->dyn.S && h->g_spawn >= 0) {
         hipLaunchKernelGGL(vf::k_spawn_tags_clear, dim3(h->dyn.Npad / vf::kBlock), dim3(vf::kBlock), 0, nullptr, h->dyn.S, h->dyn.G, h->dyn.Npad,
@@ -622,6 +644,32 @@ int vf_env_set_agent_offset(vf_env* h, int64_t first_agent)
 }
 
 int64_t vf_env_agent_offset(const vf_env* h) { return h ? (int64_t)h->agent0 : -1; }
+
+int vf_env_set_obstacles(vf_env* h, const vf_obstacle* t, int32_t n)
+{
+    if (!h) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: null handle");
+    if (n < 0 || n > VF_MAX_OBSTACLES) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: n = %d outside 0..%d", n, VF_MAX_OBSTACLES);
+    if (n > 0 && !t) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: null table");
+    for (int k = 0; k < n; ++k) {
+        const vf_obstacle& o = t[k];
+        if (o.type < VF_OBST_SPHERE || o.type > VF_OBST_PILLAR) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: unknown type %d", k, o.type);
+        bool finite = std::isfinite(o.r);
+        for (int d = 0; d < 3; ++d) finite = finite && std::isfinite(o.a[d]) && std::isfinite(o.b[d]);
+        if (!finite) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: non-finite value", k);
+        if (o.type != VF_OBST_BOX && !(o.r > 0.0f)) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: radius must be > 0", k);
+        if (o.type == VF_OBST_BOX && !(o.a[0] < o.b[0] && o.a[1] < o.b[1] && o.a[2] < o.b[2]))
+            return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: box needs lo < hi in every component", k);
+        if (o.type == VF_OBST_PILLAR && !(o.a[2] < o.b[2])) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: pillar needs z_lo < z_hi", k);
+    }
+    // (as vf_env_set_agent_offset: a launch of this handle still in flight must not see the block change under it)
+    VF_HIP(hipDeviceSynchronize());
+    if (int rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg, t, n)) return rc;
+    for (int k = 0; k < n; ++k) h->obst[k] = t[k];
+    h->n_obst = n;
+    return VF_OK;
+}
+
+int32_t vf_env_obstacle_count(const vf_env* h) { return h ? h->n_obst : -1; }
 
 int64_t vf_env_slab_floats(const vf_env* h) { return h ? (int64_t)h->dyn.Npad * h->dyn.G * 4 : 0; }
 
@@ -647,9 +695,9 @@ int vf_env_reset(vf_env* h, const int32_t* idx, int32_t k, const float* full_sta
     hipStream_t st = vf::as_stream(stream);
     const dim3 grid(vf::blocks_for(n)), block(vf::kBlock);
     switch (h->cfg.kind) {
-    case VF_ENV_HOVER: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.cfg, h->cfg, r); break;
-    case VF_ENV_NAV: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_NAV>, grid, block, 0, st, h->dyn.cfg, h->cfg, r); break;
-    default: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_RACING>, grid, block, 0, st, h->dyn.cfg, h->cfg, r); break;
+    case VF_ENV_HOVER: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    case VF_ENV_NAV: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_NAV>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    default: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_RACING>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
     }
     VF_HIP(hipGetLastError());
     return VF_OK;
@@ -721,6 +769,9 @@ int vf_env_rollout_fused(vf_env* h, const vf_env_rollout* r, vf_stream_t stream)
 {
     if (int rc = check_rollout(h, r, "vf_env_rollout_fused")) return rc;
     if (r->action_stride % 4) return vf::fail(VF_EINVAL, "vf_env_rollout_fused: action_stride must be a multiple of 4 floats");
+    if (h->n_obst > 0)
+        return vf::fail(VF_EUNSUPPORTED, "vf_env_rollout_fused: the handle has an obstacle table (vf_env_set_obstacles); the K-step kernel "
+                                         "knows the bare room box only: use vf_env_step_n");
     vf::EnvArgs g{dyn_args(h, r->actions, r->out.obs), r->out, h->g_race, r->auto_reset};
     g.out.done_list = g.out.done_count = nullptr;
     g.K = r->K;
@@ -804,25 +855,31 @@ int vf_env_finish_step(vf_env* h, const float* ext_collision_point, const uint8_
     g.ext_oob = ext_out_bounds;
     const dim3 grid(h->dyn.Npad / vf::kBlock), block(vf::kBlock);
     hipStream_t st = vf::as_stream(stream);
-    switch (h->cfg.kind) {
-    case VF_ENV_HOVER: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    case VF_ENV_NAV: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_NAV>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    default: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_RACING>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    const int key = h->cfg.kind * 2 + (h->n_obst > 0 ? 1 : 0);
+    switch (key) {
+    case VF_ENV_HOVER * 2: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_HOVER * 2 + 1: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_HOVER, true>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_NAV * 2: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_NAV>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_NAV * 2 + 1: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_NAV, true>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_RACING * 2: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_RACING>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    default: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_RACING, true>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
     }
     VF_HIP(hipGetLastError());
     h->stale_all = 1;        // re-spawns of the split step are not reflected in the stale bits
     return VF_OK;
 }
 
-int vf_env_query(vf_env* h, const vf_env_view* view, vf_stream_t stream)
+int vf_env_query_ext(vf_env* h, const vf_env_view* view, const float* ext_collision_point, const uint8_t* skip, vf_stream_t stream)
 {
     if (!h || !view) return vf::fail(VF_EINVAL, "vf_env_query: null argument");
     if (!h->dyn.S) return vf::fail(VF_ESTATE, "vf_env_query: vf_env_bind has not been called");
     hipLaunchKernelGGL(vf::k_env_query, dim3(vf::blocks_for(h->dyn.N)), dim3(vf::kBlock), 0, vf::as_stream(stream),
-                       h->dyn.cfg, h->cfg, dyn_args(h, nullptr, nullptr), h->g_race, *view);
+                       h->dyn.cfg, h->d_cfg, dyn_args(h, nullptr, nullptr), h->g_race, *view, ext_collision_point, skip);
     VF_HIP(hipGetLastError());
     return VF_OK;
 }
+
+int vf_env_query(vf_env* h, const vf_env_view* view, vf_stream_t stream) { return vf_env_query_ext(h, view, nullptr, nullptr, stream); }
 
 int vf_env_time_steps(vf_env* h, const float* action, const vf_env_out* out, int32_t auto_reset, int32_t iters,
                       vf_stream_t stream, float* mean_us)

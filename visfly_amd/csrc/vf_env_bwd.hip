@@ -19,17 +19,18 @@ namespace vf {
 // WIND: the step ran with per-agent wind rows (BwdArgsWind::wind, N rows); the no-wind instances are the code they were without the parameter
 template <bool WIND> using BwdArgsOf = std::conditional_t<WIND, BwdArgsWind, BwdArgs>;
 
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool WIND = false>
+// OBST: the handle has an obstacle table (Navigation kind only: the hover and racing rewards read nothing of the collision)
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool WIND = false, bool OBST = false>
 __global__ __launch_bounds__(kBlock) void k_env_step_bwd(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, const BwdArgsOf<WIND> g)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [S*kSave][kBlock]
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= ((g.N + kBlock - 1) / kBlock) * kBlock) return;
     if constexpr (WIND)
-        env_step_bwd_agent<KIND, ACT, INTEG, CTRL_DELAY, kBlock, false, false, true>(*cp, *ep, g, i, i < g.N, lds + threadIdx.x, nullptr, nullptr,
-                                                                                     nullptr, nullptr, nullptr, g.wind);
+        env_step_bwd_agent<KIND, ACT, INTEG, CTRL_DELAY, kBlock, false, false, true, OBST>(*cp, *ep, g, i, i < g.N, lds + threadIdx.x, nullptr, nullptr,
+                                                                                           nullptr, nullptr, nullptr, g.wind);
     else
-        env_step_bwd_agent<KIND, ACT, INTEG, CTRL_DELAY, kBlock>(*cp, *ep, g, i, i < g.N, lds + threadIdx.x);
+        env_step_bwd_agent<KIND, ACT, INTEG, CTRL_DELAY, kBlock, false, false, false, OBST>(*cp, *ep, g, i, i < g.N, lds + threadIdx.x);
 }
 
 }  // namespace vf
@@ -38,19 +39,19 @@ namespace {
 
 template <bool WIND> using BwdKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::BwdArgsOf<WIND>);
 
-template <int KIND, bool WIND>
+template <int KIND, bool WIND, bool OBST = false>
 BwdKernel<WIND> pick_bwd(const vf_dyn_cfg& c)
 {
     const int key = (c.integrator == VF_INT_RK4 ? 4 : 0) | (c.action_type == VF_ACT_BODYRATE ? 2 : 0) | (c.ctrl_delay ? 1 : 0);
     switch (key) {
-    case 0: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_EULER, false, WIND>;
-    case 1: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_EULER, true, WIND>;
-    case 2: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_EULER, false, WIND>;
-    case 3: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_EULER, true, WIND>;
-    case 4: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_RK4, false, WIND>;
-    case 5: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_RK4, true, WIND>;
-    case 6: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_RK4, false, WIND>;
-    default: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_RK4, true, WIND>;
+    case 0: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_EULER, false, WIND, OBST>;
+    case 1: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_EULER, true, WIND, OBST>;
+    case 2: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_EULER, false, WIND, OBST>;
+    case 3: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_EULER, true, WIND, OBST>;
+    case 4: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_RK4, false, WIND, OBST>;
+    case 5: return vf::k_env_step_bwd<KIND, VF_ACT_THRUST, VF_INT_RK4, true, WIND, OBST>;
+    case 6: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_RK4, false, WIND, OBST>;
+    default: return vf::k_env_step_bwd<KIND, VF_ACT_BODYRATE, VF_INT_RK4, true, WIND, OBST>;
     }
 }
 
@@ -66,8 +67,9 @@ int launch_bwd(BwdKernel<WIND> k, int S, int Npad, vf_stream_t stream, const vf_
 }
 
 template <bool WIND>
-BwdKernel<WIND> pick_env_bwd(int kind, const vf_dyn_cfg& c)
+BwdKernel<WIND> pick_env_bwd(int kind, const vf_dyn_cfg& c, bool obst)
 {
+    if (obst && kind == VF_ENV_NAV) return pick_bwd<VF_ENV_NAV, WIND, true>(c);     // (the other kinds' rewards read nothing of the collision)
     return kind == VF_ENV_RACING ? pick_bwd<VF_ENV_RACING, WIND>(c) : (kind == VF_ENV_NAV ? pick_bwd<VF_ENV_NAV, WIND>(c) : pick_bwd<VF_ENV_HOVER, WIND>(c));
 }
 
@@ -91,9 +93,9 @@ int env_step_bwd(vf_env* h, const vf_env_bwd_args* a, const float* wind, vf_stre
     const vf::BwdArgs g{h->dyn.N, h->dyn.G, h->dyn.g_drag, h->g_race, a->tape_slab, reinterpret_cast<const float4*>(a->action),
                         a->d_obs, a->d_reward, a->done, a->adj_slab, reinterpret_cast<float4*>(a->d_action)};
     if (wind)
-        return launch_bwd<true>(pick_env_bwd<true>(h->cfg.kind, h->dyn.cfg), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg,
+        return launch_bwd<true>(pick_env_bwd<true>(h->cfg.kind, h->dyn.cfg, h->n_obst > 0), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg,
                                 vf::BwdArgsWind{g, reinterpret_cast<const float4*>(wind)});
-    return launch_bwd<false>(pick_env_bwd<false>(h->cfg.kind, h->dyn.cfg), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg, g);
+    return launch_bwd<false>(pick_env_bwd<false>(h->cfg.kind, h->dyn.cfg, h->n_obst > 0), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg, g);
 }
 
 // Dynamics.step's own reverse pass (SURVEY 8b.4 `vf_dyn_step_bwd`): what autograd does for a loss on the states a bare

@@ -128,7 +128,9 @@ __device__ __forceinline__ void derivs_bwd(const vf_dyn_cfg& c, const Quat& q, c
 // the constant vf_dyn_cfg.wind: the replay and the reward terms read that row.  On the reference's tape the wind is a constant of the
 // step (it depends on the agent's time and its own previous value only), so no adjoint flows into it.  WIND = false compiles to the
 // code without the parameter.
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, int STRIDE, bool CKPT = false, bool QUAD = false, bool WIND = false>
+// OBST (Navigation kind, launch-by-launch adjoint only): the step ran with the handle's obstacle table -- the closest point the reward read
+// is scene_collision's; a constant of the step, like the box face
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, int STRIDE, bool CKPT = false, bool QUAD = false, bool WIND = false, bool OBST = false>
 __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf_env_cfg& e, const BwdArgs& g, int i, bool live, float* lds_col,
                                                    const float4* rec = nullptr, QuadCarry* carry = nullptr, const float* d_obs_lds = nullptr,
                                                    float* d_action_lds = nullptr, const QuadLane* quad = nullptr, const float4* wind = nullptr)
@@ -379,11 +381,11 @@ __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf
     } else if (live && g.d_reward && KIND == VF_ENV_NAV) {
         // NavigationEnv.get_reward (envs/NavigationEnv.py:84-99).  What autograd differentiates there: position, orientation,
         // velocity, angular velocity and -- through collision_vector = collision_point.detach() - position
-        // (droneEnv.py:345-366) -- the distance / direction to the closest bbox face; success and the step counter are
+        // (droneEnv.py:345-366) -- the distance / direction to the closest scene point (bbox face, or OBST: the obstacle table's); success and the step counter are
         // constants.  clamp / clamp_max / clamp_min pass the gradient on the closed side, relu'(0) = 0, norm'(0) = 0.
         const float dr = dr_in;
         const float vv[3] = {s.v[0] + wnd[0], s.v[1] + wnd[1], s.v[2] + wnd[2]};
-        const Collision col = bbox_collision(e, s.p);
+        const Collision col = collision_query<OBST>(e, s.p);
         const bool success = norm3(s.p[0] - e.target[0], s.p[1] - e.target[1], s.p[2] - e.target[2]) <= e.success_radius;
         const int step_count = __float_as_int(sp.omg) + 1;        // counter of THIS step (the tape holds the pre-step slab)
         float ltp[3] = {0.f, 0.f, 0.f}, lcv[3] = {0.f, 0.f, 0.f}, ldis = 0.0f;

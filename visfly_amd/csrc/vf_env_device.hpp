@@ -64,6 +64,60 @@ __device__ __forceinline__ Collision bbox_collision(const vf_env_cfg& e, const f
     return c;
 }
 
+// The closest scene point over the room box and the handle's obstacle table (include/visfly_amd.h "Analytic obstacles"): candidate 0 is
+// the box query above, candidate 1 + k obstacle k; the smallest distance g wins, the first on a tie.  Plain fp32 operations in the stated
+// order (this header runs under fp contract(off)); from the winner's point the vector, the distance and the hit test are formed as for an
+// external scene point (env_epilogue, EXT).  `e` must be the handle's device block (env_scene): the entry count, the loop counter and
+// with them every table entry and its type are wave-uniform -- scalar loads, a type switch that does not diverge
+__device__ __forceinline__ Collision scene_collision(const vf_env_cfg& e, const float* p)
+{
+    Collision c = bbox_collision(e, p);
+    const vf_env_scene& sc = env_scene(e);
+    float best = sqrtf((c.vec[0] * c.vec[0] + c.vec[1] * c.vec[1]) + c.vec[2] * c.vec[2]);
+    const int n = sc.n_obst;
+#pragma unroll 1
+    for (int k = 0; k < n; ++k) {
+        const vf_obstacle& o = sc.obst[k];
+        float q[3], g;
+        if (o.type == VF_OBST_SPHERE) {
+            const float dx[3] = {p[0] - o.a[0], p[1] - o.a[1], p[2] - o.a[2]};
+            const float d = sqrtf((dx[0] * dx[0] + dx[1] * dx[1]) + dx[2] * dx[2]);
+            g = fmaxf(d - o.r, 0.0f);
+            const float s = o.r / d;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) q[j] = d <= o.r ? p[j] : o.a[j] + dx[j] * s;
+        } else if (o.type == VF_OBST_BOX) {
+            float ev[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { q[j] = fminf(fmaxf(p[j], o.a[j]), o.b[j]); ev[j] = p[j] - q[j]; }
+            g = sqrtf((ev[0] * ev[0] + ev[1] * ev[1]) + ev[2] * ev[2]);
+        } else {   // VF_OBST_PILLAR: axis (a[0], a[1]), z in [a[2], b[2]]
+            const float dx = p[0] - o.a[0], dy = p[1] - o.a[1];
+            const float dxy = sqrtf(dx * dx + dy * dy);
+            const float er = fmaxf(dxy - o.r, 0.0f);
+            q[2] = fminf(fmaxf(p[2], o.a[2]), o.b[2]);
+            const float ez = p[2] - q[2];
+            g = sqrtf(er * er + ez * ez);
+            const float s = dxy > o.r ? o.r / dxy : 1.0f;
+            q[0] = o.a[0] + dx * s;
+            q[1] = o.a[1] + dy * s;
+        }
+        if (g < best) { best = g; c.cp[0] = q[0]; c.cp[1] = q[1]; c.cp[2] = q[2]; }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) c.vec[d] = c.cp[d] - p[d];
+    c.dis = norm3(c.vec[0], c.vec[1], c.vec[2]);
+    c.hit = c.dis < e.uav_radius;
+    return c;
+}
+// the step's collision query: the table (OBST) or the bare room box
+template <bool OBST, bool NO_ROOT = false>
+__device__ __forceinline__ Collision collision_query(const vf_env_cfg& e, const float* p)
+{
+    if constexpr (OBST) return scene_collision(e, p);
+    else return bbox_collision<NO_ROOT>(e, p);
+}
+
 // HoverEnv.get_reward (envs/HoverEnv.py:83-94), also the positional RacingEnv reward
 // PAIRED: the four norms' square roots as one sqrt_p2 (vf_pair_algebra.hpp), the same operations
 template <bool PAIRED = false>

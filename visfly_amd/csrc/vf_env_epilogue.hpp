@@ -120,7 +120,9 @@ __device__ __forceinline__ SpawnSlot load_spawn_slot(const EnvArgs& g, int i, bo
 // 0.3 us off the headline regime only, profiles/r04_env_quad.txt; not kept)
 // STRAIGHT (k_env_step<STRAIGHT>, vf_env.hip): the rows are known on the host to be the raw state rows, obs_mode is not read; the hover
 // reward's square roots are taken as pairs and the hover kind's collision test without its root -- the same results, bit for bit
-template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false, int STRAIGHT = 0>
+// OBST: the handle has an obstacle table (vf_env_set_obstacles): the closest scene point is scene_collision's, over the room box and the
+// table, here and for the re-spawn; everything downstream of the point is the same code.  Picked on the host only while the table is non-empty
+template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false, int STRAIGHT = 0, bool OBST = false>
 __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_cfg& e, const EnvArgs& g, int i, bool live,
                                              Agent& s, Spares& sp, int wave_first, float* tile, float* reward_reg = nullptr,
                                              bool* done_reg = nullptr, unsigned long long* tr = nullptr,   // tr: -DVF_ENV_TRACE builds only
@@ -135,7 +137,8 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
     const float vel[3] = {s.v[0] + s.wnd[0], s.v[1] + s.wnd[1], s.v[2] + s.wnd[2]};  // dynamics.py:751-752
     // (the hover kind reads nothing of the collision but its flags, the navigation reward reads the distance)
     constexpr bool NO_ROOT = (STRAIGHT & 4) && KIND == VF_ENV_HOVER && !EXT;
-    Collision col = bbox_collision<NO_ROOT>(e, s.p);
+    static_assert(!(OBST && STRAIGHT), "the straight-line instances know the bare room box only");
+    Collision col = collision_query<OBST, NO_ROOT>(e, s.p);
     if constexpr (EXT) {   // visual branch of update_collision (droneEnv.py:330-342,364-367): the scene manager's closest point
         if (g.ext_point && live) {
             const float* q = g.ext_point + 3 * (size_t)i;
@@ -286,7 +289,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
             *granule(g.d.S, g.d.G, i, g.d.g_drag) = kl4;
             *granule(g.d.S, g.d.G, i, g.d.g_drag + 1) = kq4;
         }
-        col = bbox_collision<NO_ROOT>(e, s.p);                                              // droneEnv.py:285-288
+        col = collision_query<OBST, NO_ROOT>(e, s.p);                                       // droneEnv.py:285-288
         er.flags = (int)(episode << 8);
         er.flags = set_flag(er.flags, VF_F_COLLISION, col.hit);
         er.flags = set_flag(er.flags, VF_F_OUT_BOUNDS, col.oob);

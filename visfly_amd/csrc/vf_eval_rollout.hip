@@ -61,6 +61,7 @@ extern "C" int vf_eval_rollout(vf_env* h, const vf_mlp_desc* desc, const float* 
         if (desc->layer[l].save) return vf::fail(VF_EINVAL, "vf_eval_rollout: the layer table must not keep activation copies (layer %d has a save pointer)", l);
     if (!h->dyn.S) return vf::fail(VF_ESTATE, "vf_eval_rollout: vf_env_bind has not been called");
     if (h->dyn.wind) return vf::fail(VF_EUNSUPPORTED, "vf_eval_rollout: per-agent wind rows are set");
+    if (h->n_obst > 0) return vf::fail(VF_EUNSUPPORTED, "vf_eval_rollout: the handle has an obstacle table (vf_env_set_obstacles): step launch by launch");
     const int N = h->dyn.N, T = a->T_max;
     const bool race2 = h->cfg.kind == VF_ENV_RACING && h->cfg.obs_mode == VF_OBS_RACE2;      // RacingEnv2: 16 gate-relative columns
     const int OW = race2 ? 16 : 13;

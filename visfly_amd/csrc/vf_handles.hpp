@@ -39,11 +39,15 @@ struct vf_env {
     // next helper pass (after a reset, or after launches that re-spawn agents without maintaining the bits)
     unsigned long long* d_stale = nullptr;
     int stale_all = 1;
-    // device constant block, see vf_dyn::d_cfg: the first member of a vf_env_dev {cfg, agent0} (vf_common.hpp; upload_env_dev)
+    // device constant block, see vf_dyn::d_cfg: the first member of a vf_env_scene {{cfg, agent0, hit_y}, obstacle table} (vf_common.hpp; upload_env_dev)
     vf_env_cfg* d_cfg = nullptr;
     // global id of row 0 (vf_env_set_agent_offset): every Philox counter keyed by agent uses agent0 + row, so a contiguous shard of a
     // population draws exactly what those rows of the whole population draw.  0: rows are their own ids
     unsigned agent0 = 0;
+    // obstacle table (vf_env_set_obstacles): the host copy of what the device block carries behind the cfg.  Non-empty: the step, reset,
+    // query and adjoint launches take their OBST instances, the persistent launches refuse
+    vf_obstacle obst[VF_MAX_OBSTACLES] = {};
+    int n_obst = 0;
 };
 
 namespace vf {
@@ -95,11 +99,15 @@ inline int upload_dyn_dev(const vf_dyn_cfg& cfg, vf_dyn_cfg** dev)
     return VF_OK;
 }
 // an env handle's block: cfg + agent0 (allocated on first use, rewritten in place afterwards: the kernels keep the address)
-inline int upload_env_dev(const vf_env_cfg& cfg, unsigned agent0, vf_env_cfg** dev)
+// ... + the obstacle table (vf_env_scene; n_obst entries of `obst`, 0 = the bare room box)
+inline int upload_env_dev(const vf_env_cfg& cfg, unsigned agent0, vf_env_cfg** dev, const vf_obstacle* obst = nullptr, int n_obst = 0)
 {
-    const vf_env_dev host{cfg, agent0, hit_threshold(cfg.uav_radius)};
-    if (!*dev) VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(vf_env_dev)));
-    VF_HIP(hipMemcpy(*dev, &host, sizeof(vf_env_dev), hipMemcpyHostToDevice));
+    vf_env_scene host{};
+    host.dev = vf_env_dev{cfg, agent0, hit_threshold(cfg.uav_radius)};
+    host.n_obst = n_obst;
+    for (int k = 0; k < n_obst; ++k) host.obst[k] = obst[k];
+    if (!*dev) VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(vf_env_scene)));
+    VF_HIP(hipMemcpy(*dev, &host, sizeof(vf_env_scene), hipMemcpyHostToDevice));
     return VF_OK;
 }
 template <class T>

@@ -36,6 +36,7 @@ extern "C" int vf_ppo_rollout(vf_env* h, const vf_mlp_desc* desc, const float* p
         if (desc->layer[l].save) return vf::fail(VF_EINVAL, "vf_ppo_rollout: the layer table must not keep activation copies (layer %d has a save pointer)", l);
     if (!h->dyn.S) return vf::fail(VF_ESTATE, "vf_ppo_rollout: vf_env_bind has not been called");
     if (h->dyn.wind) return vf::fail(VF_EUNSUPPORTED, "vf_ppo_rollout: per-agent wind rows are set");
+    if (h->n_obst > 0) return vf::fail(VF_EUNSUPPORTED, "vf_ppo_rollout: the handle has an obstacle table (vf_env_set_obstacles): step launch by launch");
     // (observation / reward variants -- HoverEnv2, NavigationEnv2 -- are the epilogue's own: the rows it stages through the wave's
     // tile for the next forward are already in the env's obs_mode, the terminal rows too; r05)
     if ((reinterpret_cast<uintptr_t>(a->means) | reinterpret_cast<uintptr_t>(a->actions) | reinterpret_cast<uintptr_t>(a->stat)) & 15)

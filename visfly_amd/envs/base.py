@@ -30,6 +30,7 @@ from ..constants import derive_constants
 from ..dynamics import Dynamics
 from ..type import TensorDict
 from . import spaces
+from .obstacles import obstacle_table, parse_obstacles
 from .persistent import PersistentLaunches
 from .randomization import ReplaySpawner, spawn_boxes
 
@@ -140,7 +141,7 @@ def _imu_noise_model(random_kwargs):
 def _reject_unsupported(scene_kwargs, sensor_kwargs):
     """With visual=False the reference never renders (droneEnv.py:296-333 reads the sensors only if self.visual) and forces the
     empty box scene (:69-71), so visual sensors / scene objects change nothing there either -- say so once instead of
-    dropping them silently."""
+    dropping them silently.  (scene_kwargs["obstacles"] is this library's own key: the analytic solids of envs/obstacles.py.)"""
     import warnings
     visual = [s.get("uuid") for s in (sensor_kwargs or []) if "IMU" not in str(s.get("uuid", ""))]
     if visual:
@@ -149,7 +150,7 @@ def _reject_unsupported(scene_kwargs, sensor_kwargs):
     ignored = [k for k in ("obj_settings", "render_settings", "update_approaching_info", "path") if (scene_kwargs or {}).get(k)]
     if ignored:
         warnings.warn(f"visfly_amd: scene_kwargs {ignored} have no effect with visual=False (collisions use the "
-                      "[-30,-30,0]..[30,30,8] box of droneEnv.py:129)", stacklevel=4)
+                      "[-30,-30,0]..[30,30,8] box of droneEnv.py:129 and scene_kwargs['obstacles'])", stacklevel=4)
 
 
 class DroneEnvsBase:
@@ -295,6 +296,7 @@ class DroneGymEnvsBase(PersistentLaunches):
         self._boxes = spawn_boxes(random_kwargs)
         self._imu_noise = _imu_noise_model(random_kwargs)
         _reject_unsupported(scene_kwargs, sensor_kwargs)     # warns
+        obstacles = parse_obstacles((scene_kwargs or {}).get("obstacles"))     # raises before any device work
         self.target = th.as_tensor([1., 0., 1.5] if target is None else target, dtype=th.float32).reshape(3)
         self.success_radius = success_radius
         self.targets = None if gates is None else th.as_tensor(gates, dtype=th.float32)
@@ -337,6 +339,9 @@ class DroneGymEnvsBase(PersistentLaunches):
             self._h = h
             if self.agent_offset is not None:
                 _lib.check(L.vf_env_set_agent_offset(h, self.agent_offset))
+            self._obstacles = []
+            if obstacles:
+                self._set_obstacles(obstacles)
             G = int(L.vf_env_granules(h))
             floats = int(L.vf_env_slab_floats(h))
             self._slab = th.zeros((floats // (G * TILE * 4), G, TILE, 4), dtype=th.float32, device=self.device)
@@ -391,6 +396,35 @@ class DroneGymEnvsBase(PersistentLaunches):
     def _stream(self):
         return _lib.current_stream(self.device)
 
+    def _set_obstacles(self, parsed):
+        with th.cuda.device(self.device):
+            _lib.check(_lib.lib().vf_env_set_obstacles(self._h, obstacle_table(parsed), len(parsed)))
+        self._obstacles = parsed
+        # the persistent launches know the bare room box only: with a table every trainer steps launch by launch (as for TrackEnv)
+        if parsed:
+            self._PERSISTENT = False
+        else:
+            self.__dict__.pop("_PERSISTENT", None)       # back to the class's own answer
+        self._qcache = None
+        for ro in getattr(self, "_rollouts", {}).values():       # a captured graph holds the kernels of the table it was captured with
+            for g in ro["graphs"].values():
+                _lib.lib().vf_env_graph_destroy(g)
+            ro["graphs"] = {}
+
+    @property
+    def obstacles(self):
+        """the env's analytic obstacles (envs/obstacles.py: sphere / box / pillar dicts, at most 16, shared by all agents): the closest
+        scene point of every collision query is taken over the room box and these solids, inside the fused step.  Assignable between
+        steps ([] clears the table); the flags of the current state follow at the next step or reset, the collision_* properties at
+        once."""
+        return [dict(o) for o in self._obstacles]
+
+    @obstacles.setter
+    def obstacles(self, value):
+        if getattr(self, "_half_step", False):
+            raise VisflyError("obstacles: step_begin() is waiting for its step_finish()")
+        self._set_obstacles(parse_obstacles(value))
+
     def _out(self, obs, reward, done):
         o = _lib.EnvOut()
         o.obs, o.reward, o.done = _lib.ptr(obs), _lib.ptr(reward), _lib.ptr(done)
@@ -435,15 +469,12 @@ class DroneGymEnvsBase(PersistentLaunches):
             v = _lib.EnvView()
             for k, t in q.items():
                 setattr(v, k, _lib.ptr(t))
+            # after step_finish(collision_point=...): the scene's closest point, except where the agent re-spawned; vector and distance by
+            # the step kernel's own arithmetic (a torch norm is another rounding sequence than the one is_collision was decided with)
+            cp, done = getattr(self, "_ext_col", None) or (None, None)
             with th.cuda.device(dev):
-                _lib.check(_lib.lib().vf_env_query(self._h, C.byref(v), self._stream()))
-            ext = getattr(self, "_ext_col", None)
-            if ext is not None:      # after step_finish(collision_point=...): the scene's closest point, except where the agent re-spawned
-                cp, done = ext
-                keep = done.view(-1, 1)
-                q["col_point"] = th.where(keep, q["col_point"], cp)
-                q["col_vec"] = th.where(keep, q["col_vec"], cp - self.envs.dynamics.position)
-                q["col_dis"] = th.where(done, q["col_dis"], q["col_vec"].norm(dim=1))
+                _lib.check(_lib.lib().vf_env_query_ext(self._h, C.byref(v), _lib.ptr(cp), None if done is None else done.data_ptr(),
+                                                       self._stream()))
             self._qcache = q
         return self._qcache
 
@@ -720,6 +751,9 @@ class DroneGymEnvsBase(PersistentLaunches):
             a = th.as_tensor(np.asarray(a) if not isinstance(a, th.Tensor) else a).to(dev, dtype=th.float32).contiguous()
         if a.dim() != 3 or a.shape[1:] != (N, 4):
             raise ValueError(f"step_n expects actions of shape (K,{N},4), got {tuple(a.shape)}")
+        if fused and self._obstacles:
+            raise ValueError("step_n(fused=True): the env has obstacles and the K-step kernel knows the bare room box only; "
+                             "use step_n() or step_n(graph=True)")
         K = a.shape[0]
         if self.validate_actions:
             assert a.max() <= 1 and a.min() >= -1
