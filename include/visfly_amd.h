@@ -323,7 +323,9 @@ int64_t vf_env_agent_offset(const vf_env* h);   /* the value set, 0 by default; 
  * out-of-bounds stays the room box's test.  The navigation adjoint treats cp as a constant of the step (collision_point.detach()).
  * Followed by vf_env_step, vf_env_step_n, vf_env_graph_*, vf_env_reset, vf_env_query, vf_env_step_bwd(_wind) and vf_env_finish_step (an
  * external point, where given, still wins).  While the table is non-empty vf_env_rollout_fused, vf_ppo_rollout, vf_bptt_rollout,
- * vf_bptt_reverse and vf_eval_rollout return VF_EUNSUPPORTED before any launch.
+ * vf_bptt_reverse and vf_eval_rollout return VF_EUNSUPPORTED before any launch.  Every scene can have a table of its own instead
+ * (vf_env_set_scene_obstacles, below), and device-drawn spawns can be kept clear of the table (vf_env_set_safe_spawn, below); oriented or
+ * moving solids, meshes, depth images and tables inside the persistent launches are not built.
  * vf_env_set_obstacles: host_table = n entries (n = 0 clears the table; host_table may then be NULL); VF_EINVAL for n < 0, n >
  * VF_MAX_OBSTACLES, an unknown type, a non-finite value, r <= 0 (sphere, pillar) or lo >= hi in any component (box; pillar: z_lo >= z_hi).
  * Rewrites the handle's device constant block after a device-wide synchronisation; a captured vf_env_graph keeps the kernels it was
@@ -337,7 +339,31 @@ typedef struct vf_obstacle {
     float r;
 } vf_obstacle;
 int vf_env_set_obstacles(vf_env* h, const vf_obstacle* host_table, int32_t n);
-int32_t vf_env_obstacle_count(const vf_env* h);   /* entries of the table; -1 for a null handle */
+int32_t vf_env_obstacle_count(const vf_env* h);   /* entries of the table (per-scene tables: of the largest one); -1 for a null handle */
+
+/* Per-scene tables (additive within ABI 11).  Row i of the handle belongs to scene i / agents_per_scene (the reference's layout: agents
+ * scene by scene), and every scene has a table of its own: host_tables[s][0 .. counts[s]).  The query is the one above, entry for entry;
+ * only the table and its count are the scene's.  n_scenes * agents_per_scene must equal the handle's N, every count lies in
+ * 0 .. VF_MAX_OBSTACLES and every entry in use passes vf_env_set_obstacles' checks, else VF_EINVAL naming the scene and the entry; a refused
+ * call changes nothing.  The tables live in a device buffer of the handle.  The two forms replace each other: this call clears the
+ * shared table, vf_env_set_obstacles (any n) drops the per-scene tables, n_scenes = 0 clears them.  A wave whose rows share a scene (always
+ * when agents_per_scene is a multiple of 64) reads its table through wave-uniform loads, a wave that straddles scenes lane by lane: the
+ * same operations in the same order, the same bits.  vf_env_obstacle_count then reports the largest per-scene count, and everything that
+ * refuses a shared table refuses these: vf_env_rollout_fused, vf_ppo_rollout, vf_bptt_rollout, vf_bptt_reverse, vf_eval_rollout. */
+int vf_env_set_scene_obstacles(vf_env* h, const vf_obstacle* host_tables /* [n_scenes][VF_MAX_OBSTACLES] */,
+                               const int32_t* counts /* [n_scenes] */, int32_t n_scenes, int32_t agents_per_scene);
+int32_t vf_env_scene_count(const vf_env* h);   /* 0: no per-scene tables; -1: null handle */
+
+/* Collision-free spawns (safe_generate, utils/randomization.py:64-96).  While the handle has a table (shared or per scene) and
+ * clearance > 0, every state the DEVICE draws -- vf_env_reset without full_state, the auto-reset of a step, the prefetched re-spawn copy
+ * -- is re-drawn until the step's own query at its position (the agent's scene, room box included) gives dis >= clearance.  Attempt
+ * a = 0, 1, ... draws the whole state (position, Euler angles, velocity, body rates, union pick, t) from the Philox blocks
+ * {id, episode, b + 8 a, 0x5eed}, b = 0, 1, 2: attempt 0 is the single draw of a handle without the setting, bit for bit; the drag factors
+ * (blocks 4, 5) stay one draw per episode.  At most VF_SPAWN_TRIES attempts: the last candidate is kept whatever the query says (the
+ * reference loops on behind a warning).  clearance = uav_radius makes "rejected" the step's is_collision.  clearance <= 0: off, the
+ * default; without a table the value is stored and inert.  A host-replayed reset (full_state) is never re-drawn. */
+#define VF_SPAWN_TRIES 16
+int vf_env_set_safe_spawn(vf_env* h, float clearance);
 
 /* Time-varying / per-agent wind (envs/base/dynamics.py:132-174,384-388: wind_settings given as strings are eval'ed into
  * functions of (t, previous wind) and re-evaluated by update_wind() at the top of every step; the value then holds for the

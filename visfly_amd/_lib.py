@@ -98,6 +98,7 @@ class EnvCfg(C.Structure):
 
 
 MAX_OBSTACLES = 16        # VF_MAX_OBSTACLES
+SPAWN_TRIES = 16          # VF_SPAWN_TRIES
 OBST_SPHERE, OBST_BOX, OBST_PILLAR = 0, 1, 2
 
 
@@ -321,6 +322,9 @@ SIGNATURES = {
     "vf_env_agent_offset": (C.c_int64, [_vp]),
     "vf_env_set_obstacles": (C.c_int, [_vp, C.POINTER(Obstacle), C.c_int32]),
     "vf_env_obstacle_count": (C.c_int32, [_vp]),
+    "vf_env_set_scene_obstacles": (C.c_int, [_vp, C.POINTER(Obstacle), C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
+    "vf_env_scene_count": (C.c_int32, [_vp]),
+    "vf_env_set_safe_spawn": (C.c_int, [_vp, C.c_float]),
     "vf_ppo_loss": (C.c_int, [_vp] * 10 + [C.c_int32, C.POINTER(PpoLossCfg), _vp, _vp]),
     "vf_gather_rows": (C.c_int, [C.POINTER(GatherFields), _vp, C.c_int64, _vp]),
     "vf_rollout_post": (C.c_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, C.c_int32, _vp]),

@@ -76,7 +76,23 @@ struct vf_env_scene {
     int n_obst;        // entries of obst in use, 0 = the bare room box
     int pad[3];
     vf_obstacle obst[VF_MAX_OBSTACLES];
+    // per-scene tables (vf_env_set_scene_obstacles), behind everything the shared-table code reads: scene s = row / agents_per_scene owns
+    // tables[s * VF_MAX_OBSTACLES ..] and counts[s]; a device buffer of the handle, null / n_scenes = 0 without them (n_obst is 0 then too)
+    const vf_obstacle* tables;
+    const int* counts;
+    int agents_per_scene, n_scenes;
+    // vf_env_set_safe_spawn: the clearance a device-drawn spawn keeps from the agent's table, 0 = one draw (and 0 while the handle has no table)
+    float clearance;
+    int pad2;
 };
+// what a handle keeps of that tail on the host (upload_env_dev)
+struct vf_scene_tail {
+    vf_obstacle* tables = nullptr;     // device: [n_scenes][VF_MAX_OBSTACLES], the counts ([n_scenes] int) behind them in the same buffer
+    int agents_per_scene = 0, n_scenes = 0;
+    float clearance = 0.0f;
+};
+// the obstacle-table form a kernel instance is compiled for (template parameter OBST)
+constexpr int VF_TABLE_NONE = 0, VF_TABLE_SHARED = 1, VF_TABLE_SCENES = 2;
 
 #ifdef __HIPCC__
 // `e` must be the handle's device block (what the step / roll-out kernels get through their pointer argument), NOT a by-value copy

@@ -50,8 +50,9 @@ namespace vf {
 // the episode-end block, the re-spawn, the optional episode outputs behind `if (done)`, the partial / unaligned store path, the delay
 // ring (delay_steps is a preloaded scalar) and is_collision_reset.  profiles/env_straight_line.txt
 //
-// OBST: the handle's obstacle table is not empty (env_epilogue; general instances only, picked by pick_env_kernel for every agent count)
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool LAZY_SLOT = false, bool STRAIGHT = false, bool OBST = false>
+// OBST: the handle's obstacle table, shared (VF_TABLE_SHARED) or per scene (VF_TABLE_SCENES), is not empty (env_epilogue; general instances
+// only, picked by pick_env_kernel for every agent count); the helper blocks then prefetch the accepted state of a collision-free spawn
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool LAZY_SLOT = false, bool STRAIGHT = false, int OBST = VF_TABLE_NONE>
 __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, float* S,
                                                      const float4* action, int N, int G, int head, int helper, int delay_steps,
                                                      int g_drag, const EnvArgs g0)
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
         const int nbm = g.helper;
         const int base = ((int)blockIdx.x - nbm) * kHelperSpan * kBlock + (int)threadIdx.x;
 #pragma unroll 1
-        for (int k = 0; k < kHelperSpan; ++k) spawn_helper(e, g, base + k * kBlock);
+        for (int k = 0; k < kHelperSpan; ++k) spawn_helper<OBST>(e, g, base + k * kBlock);
         return;
     }
 #ifdef VF_ENV_TRACE
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
 // in vf_dyn_step on the same slab, an external scene manager then answered the collision query for the new poses
 // (droneEnv.py:374-379 with visual=True).  With ext_point = ext_oob = null the two launches equal one vf_env_step bit for bit.
 // OBST: the handle has an obstacle table: where ext_point is null the table is queried instead of the bare box (and for every re-spawn)
-template <int KIND, bool OBST = false>
+template <int KIND, int OBST = VF_TABLE_NONE>
 __global__ __launch_bounds__(kBlock) void k_env_finish(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, const EnvArgs g)
 {
     const vf_dyn_cfg& c = *cp;
@@ -262,8 +263,9 @@ struct EnvResetArgs {
     unsigned agent0;  // vf_env::agent0 (the cfg arrives by value here: no vf_env_dev tail to read it from)
 };
 
-// ep: the handle's device block, read for the obstacle table behind the cfg (scene_collision; an empty table is the box query)
-template <int KIND>
+// ep: the handle's device block, read for the obstacle table behind the cfg (scene_collision; an empty table is the box query) and the spawn
+// clearance (spawn_agent_safe).  TABLE: the shared table (empty or not) or per-scene tables
+template <int KIND, int TABLE = VF_TABLE_SHARED>
 __global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const vf_env_cfg e, const EnvResetArgs r, const vf_env_cfg* __restrict__ ep)
 {
     const int j = blockIdx.x * kBlock + threadIdx.x;
@@ -287,10 +289,10 @@ __global__ __launch_bounds__(kBlock) void k_env_reset(const vf_dyn_cfg c, const 
         for (int d = 0; d < 4; ++d) { s.wm[d] = f[13 + d]; s.T[d] = f[17 + d]; }
         s.t = f[21];
     } else {
-        spawn_agent(e, r.agent0, i, episode, r.idx != nullptr, s);
+        spawn_agent_safe<TABLE>(e, *ep, r.agent0, i, episode, r.idx != nullptr, s);
     }
     for (int q = 0; q < c.delay_steps; ++q) *granule(r.d.S, r.d.G, i, VF_G_RING + q) = make_float4(0.f, 0.f, 0.f, 0.f);
-    const Collision col = scene_collision(*ep, s.p);
+    const Collision col = scene_collision<TABLE>(*ep, s.p, i);
     er.flags = (int)(episode << 8);
     er.flags = set_flag(er.flags, VF_F_COLLISION, col.hit);
     er.flags = set_flag(er.flags, VF_F_OUT_BOUNDS, col.oob);
@@ -330,6 +332,7 @@ __global__ __launch_bounds__(kBlock) void k_spawn_tags_clear(float* S, int G, in
 }
 
 // ext / skip: vf_env_query_ext -- the external scene point of the agents with skip[i] == 0, by the EXT arithmetic of env_epilogue
+template <int TABLE = VF_TABLE_SHARED>
 __global__ __launch_bounds__(kBlock) void k_env_query(const vf_dyn_cfg c, const vf_env_cfg* __restrict__ ep, const DynArgs d, int g_race,
                                                       const vf_env_view v, const float* __restrict__ ext, const unsigned char* __restrict__ skip)
 {
@@ -339,7 +342,7 @@ __global__ __launch_bounds__(kBlock) void k_env_query(const vf_dyn_cfg c, const 
     Spares sp;
     load_agent(d.S, d.G, i, s, sp);
     const EnvRegs er = unpack_env(sp);
-    Collision col = scene_collision(*ep, s.p);   // the handle's device block: room box + obstacle table
+    Collision col = scene_collision<TABLE>(*ep, s.p, i);   // the handle's device block: room box + the agent's obstacle table
     if (ext && !(skip && skip[i])) {
         const float* q = ext + 3 * (size_t)i;
 #pragma unroll
@@ -398,7 +401,7 @@ using EnvKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::EnvAr
 using EnvStepKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, float*, const float4*, int, int, int, int, int, int, const vf::EnvArgs);
 
 // OBST: the instances that query the handle's obstacle table (k_env_step)
-template <int KIND, int ACT, bool LAZY, bool OBST>
+template <int KIND, int ACT, bool LAZY, int OBST>
 EnvStepKernel pick_env_kernel_ka(const vf_dyn_cfg& c)
 {
     const int key = (c.integrator == VF_INT_RK4 ? 2 : 0) | (c.ctrl_delay ? 1 : 0);
@@ -410,7 +413,7 @@ EnvStepKernel pick_env_kernel_ka(const vf_dyn_cfg& c)
     }
 }
 
-template <int KIND, bool LAZY, bool OBST>
+template <int KIND, bool LAZY, int OBST>
 EnvStepKernel pick_env_kernel_kl(const vf_dyn_cfg& c)
 {
     switch (c.action_type) {
@@ -421,7 +424,7 @@ EnvStepKernel pick_env_kernel_kl(const vf_dyn_cfg& c)
     }
 }
 
-template <int KIND, bool OBST = false>
+template <int KIND, int OBST = vf::VF_TABLE_NONE>
 EnvStepKernel pick_env_kernel_k(const vf_dyn_cfg& c, bool lazy)
 {
     return lazy ? pick_env_kernel_kl<KIND, true, OBST>(c) : pick_env_kernel_kl<KIND, false, OBST>(c);
@@ -505,11 +508,19 @@ EnvStepKernel pick_env_straight_k(const vf_dyn_cfg& c)
 EnvStepKernel pick_env_kernel(const vf_env* h, const vf::EnvArgs& g)
 {
     const bool lazy = h->dyn.Npad > 2 * 65536;          // more than two waves per SIMD (k_env_step, LAZY_SLOT)
-    if (h->n_obst > 0) {                                // an obstacle table: the general kernel's OBST instances, never STRAIGHT
+    const int form = vf::table_form(h);
+    if (form == vf::VF_TABLE_SHARED) {                  // an obstacle table: the general kernel's OBST instances, never STRAIGHT
         switch (h->cfg.kind) {
-        case VF_ENV_HOVER: return pick_env_kernel_k<VF_ENV_HOVER, true>(h->dyn.cfg, lazy);
-        case VF_ENV_NAV: return pick_env_kernel_k<VF_ENV_NAV, true>(h->dyn.cfg, lazy);
-        default: return pick_env_kernel_k<VF_ENV_RACING, true>(h->dyn.cfg, lazy);
+        case VF_ENV_HOVER: return pick_env_kernel_k<VF_ENV_HOVER, vf::VF_TABLE_SHARED>(h->dyn.cfg, lazy);
+        case VF_ENV_NAV: return pick_env_kernel_k<VF_ENV_NAV, vf::VF_TABLE_SHARED>(h->dyn.cfg, lazy);
+        default: return pick_env_kernel_k<VF_ENV_RACING, vf::VF_TABLE_SHARED>(h->dyn.cfg, lazy);
+        }
+    }
+    if (form == vf::VF_TABLE_SCENES) {                  // ... or one table per scene
+        switch (h->cfg.kind) {
+        case VF_ENV_HOVER: return pick_env_kernel_k<VF_ENV_HOVER, vf::VF_TABLE_SCENES>(h->dyn.cfg, lazy);
+        case VF_ENV_NAV: return pick_env_kernel_k<VF_ENV_NAV, vf::VF_TABLE_SCENES>(h->dyn.cfg, lazy);
+        default: return pick_env_kernel_k<VF_ENV_RACING, vf::VF_TABLE_SCENES>(h->dyn.cfg, lazy);
         }
     }
     const bool straight = !lazy && g.d.g_drag < 0 && !g.d.wind && !g.out.done_list && !g.out.done_count && !g.stale && g.auto_reset &&
@@ -527,6 +538,43 @@ vf::DynArgs dyn_args(const vf_env* h, const float* action, float* obs, int ahead
 {
     return vf::DynArgs{h->dyn.N, h->dyn.G, h->dyn.g_drag, h->dyn.S, reinterpret_cast<const float4*>(action), obs,
                        vf::ring_head(&h->dyn, ahead), reinterpret_cast<const float4*>(h->dyn.wind), h->dyn.vel_strided};
+}
+
+// the handle's device block from its host state.  A shared table's count is the block's n_obst, per-scene tables ride in the tail with
+// n_obst = 0; the spawn clearance reaches the device only while there is a table to keep clear of (vf_env_set_safe_spawn)
+int upload_env(vf_env* h, unsigned agent0)
+{
+    vf::vf_scene_tail tail = h->scenes;
+    tail.clearance = (vf::table_form(h) != vf::VF_TABLE_NONE && h->clearance > 0.0f) ? h->clearance : 0.0f;
+    return vf::upload_env_dev(h->cfg, agent0, &h->d_cfg, h->obst, h->scenes.n_scenes > 0 ? 0 : h->n_obst, &tail);
+}
+
+// the prefetched re-spawn copies of a bound slab were drawn under settings that no longer hold (agent ids; the table or clearance of a
+// collision-free spawn): untag them (k_spawn_tags_clear), the helper blocks draw them again
+int clear_spawn_tags(vf_env* h)
+{
+    if (h->dyn.S && h->g_spawn >= 0) {
+        hipLaunchKernelGGL(vf::k_spawn_tags_clear, dim3(h->dyn.Npad / vf::kBlock), dim3(vf::kBlock), 0, nullptr, h->dyn.S, h->dyn.G, h->dyn.Npad,
+                           h->g_spawn);
+        VF_HIP(hipGetLastError());
+        VF_HIP(hipDeviceSynchronize());
+    }
+    h->stale_all = 1;
+    return VF_OK;
+}
+
+// vf_env_set_obstacles' checks of one entry; `who` names the call and, for per-scene tables, the scene
+int check_obstacle(const vf_obstacle& o, const char* who, int k)
+{
+    if (o.type < VF_OBST_SPHERE || o.type > VF_OBST_PILLAR) return vf::fail(VF_EINVAL, "%s: entry %d: unknown type %d", who, k, o.type);
+    bool finite = std::isfinite(o.r);
+    for (int d = 0; d < 3; ++d) finite = finite && std::isfinite(o.a[d]) && std::isfinite(o.b[d]);
+    if (!finite) return vf::fail(VF_EINVAL, "%s: entry %d: non-finite value", who, k);
+    if (o.type != VF_OBST_BOX && !(o.r > 0.0f)) return vf::fail(VF_EINVAL, "%s: entry %d: radius must be > 0", who, k);
+    if (o.type == VF_OBST_BOX && !(o.a[0] < o.b[0] && o.a[1] < o.b[1] && o.a[2] < o.b[2]))
+        return vf::fail(VF_EINVAL, "%s: entry %d: box needs lo < hi in every component", who, k);
+    if (o.type == VF_OBST_PILLAR && !(o.a[2] < o.b[2])) return vf::fail(VF_EINVAL, "%s: entry %d: pillar needs z_lo < z_hi", who, k);
+    return VF_OK;
 }
 
 // `ahead`: position of this launch in a sequence enqueued (or captured) before the handle's step counter advances
@@ -596,7 +644,7 @@ int vf_env_create(const vf_dyn_cfg* dyn, const vf_env_cfg* env, int32_t N, int32
     h->g_race = racing ? h->dyn.g_extra : -1;
     h->g_spawn = env->spawn_prefetch ? h->dyn.g_extra + racing : -1;
     int rc = vf::upload_dyn_dev(h->dyn.cfg, &h->dyn.d_cfg);
-    if (rc == VF_OK) rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg, h->obst, h->n_obst);
+    if (rc == VF_OK) rc = upload_env(h, h->agent0);
     if (rc == VF_OK && h->g_spawn >= 0 &&
         hipMalloc(reinterpret_cast<void**>(&h->d_stale), (size_t)2 * (h->dyn.Npad / 64) * sizeof(unsigned long long)) != hipSuccess) {
         h->d_stale = nullptr;            // no bits: the helper compares every tag, as before
@@ -617,6 +665,7 @@ void vf_env_destroy(vf_env* h)
     vf::release_cfg(&h->dyn.d_env_dummy);
     vf::release_cfg(&h->d_cfg);
     if (h->d_stale) (void)hipFree(h->d_stale);
+    if (h->scenes.tables) (void)hipFree(h->scenes.tables);
     delete h;
 }
 
@@ -631,16 +680,9 @@ int vf_env_set_agent_offset(vf_env* h, int64_t first_agent)
     // hipMemcpy from pageable memory returns after the copy and is ordered behind the null stream's work only: a launch of this
     // handle still in flight on another stream must not see the block change under it
     VF_HIP(hipDeviceSynchronize());
-    if (int rc = vf::upload_env_dev(h->cfg, (unsigned)first_agent, &h->d_cfg, h->obst, h->n_obst)) return rc;
+    if (int rc = upload_env(h, (unsigned)first_agent)) return rc;
     h->agent0 = (unsigned)first_agent;
-    if (h->dyn.S && h->g_spawn >= 0) {
-        hipLaunchKernelGGL(vf::k_spawn_tags_clear, dim3(h->dyn.Npad / vf::kBlock), dim3(vf::kBlock), 0, nullptr, h->dyn.S, h->dyn.G, h->dyn.Npad,
-                           h->g_spawn);
-        VF_HIP(hipGetLastError());
-        VF_HIP(hipDeviceSynchronize());
-    }
-    h->stale_all = 1;
-    return VF_OK;
+    return clear_spawn_tags(h);
 }
 
 int64_t vf_env_agent_offset(const vf_env* h) { return h ? (int64_t)h->agent0 : -1; }
@@ -650,23 +692,73 @@ int vf_env_set_obstacles(vf_env* h, const vf_obstacle* t, int32_t n)
     if (!h) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: null handle");
     if (n < 0 || n > VF_MAX_OBSTACLES) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: n = %d outside 0..%d", n, VF_MAX_OBSTACLES);
     if (n > 0 && !t) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: null table");
-    for (int k = 0; k < n; ++k) {
-        const vf_obstacle& o = t[k];
-        if (o.type < VF_OBST_SPHERE || o.type > VF_OBST_PILLAR) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: unknown type %d", k, o.type);
-        bool finite = std::isfinite(o.r);
-        for (int d = 0; d < 3; ++d) finite = finite && std::isfinite(o.a[d]) && std::isfinite(o.b[d]);
-        if (!finite) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: non-finite value", k);
-        if (o.type != VF_OBST_BOX && !(o.r > 0.0f)) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: radius must be > 0", k);
-        if (o.type == VF_OBST_BOX && !(o.a[0] < o.b[0] && o.a[1] < o.b[1] && o.a[2] < o.b[2]))
-            return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: box needs lo < hi in every component", k);
-        if (o.type == VF_OBST_PILLAR && !(o.a[2] < o.b[2])) return vf::fail(VF_EINVAL, "vf_env_set_obstacles: entry %d: pillar needs z_lo < z_hi", k);
-    }
+    for (int k = 0; k < n; ++k)
+        if (int rc = check_obstacle(t[k], "vf_env_set_obstacles", k)) return rc;
     // (as vf_env_set_agent_offset: a launch of this handle still in flight must not see the block change under it)
     VF_HIP(hipDeviceSynchronize());
-    if (int rc = vf::upload_env_dev(h->cfg, h->agent0, &h->d_cfg, t, n)) return rc;
+    vf_obstacle* dropped = h->scenes.tables;       // the shared table replaces per-scene tables
+    h->scenes.tables = nullptr;
+    h->scenes.n_scenes = h->scenes.agents_per_scene = 0;
     for (int k = 0; k < n; ++k) h->obst[k] = t[k];
     h->n_obst = n;
-    return VF_OK;
+    const int rc = upload_env(h, h->agent0);
+    if (dropped) (void)hipFree(dropped);
+    if (rc == VF_OK && h->clearance > 0.0f) return clear_spawn_tags(h);     // copies accepted against the old table
+    return rc;
+}
+
+int vf_env_set_scene_obstacles(vf_env* h, const vf_obstacle* t, const int32_t* counts, int32_t n_scenes, int32_t agents_per_scene)
+{
+    if (!h) return vf::fail(VF_EINVAL, "vf_env_set_scene_obstacles: null handle");
+    if (n_scenes < 0) return vf::fail(VF_EINVAL, "vf_env_set_scene_obstacles: n_scenes = %d < 0", n_scenes);
+    int n_max = 0;
+    if (n_scenes > 0) {
+        if (!t || !counts) return vf::fail(VF_EINVAL, "vf_env_set_scene_obstacles: null tables or counts");
+        if (agents_per_scene <= 0 || (int64_t)n_scenes * agents_per_scene != (int64_t)h->dyn.N)
+            return vf::fail(VF_EINVAL, "vf_env_set_scene_obstacles: %d scenes of %d agents are not the handle's %d agents", n_scenes,
+                            agents_per_scene, h->dyn.N);
+        for (int s = 0; s < n_scenes; ++s) {
+            if (counts[s] < 0 || counts[s] > VF_MAX_OBSTACLES)
+                return vf::fail(VF_EINVAL, "vf_env_set_scene_obstacles: scene %d: count %d outside 0..%d", s, counts[s], VF_MAX_OBSTACLES);
+            char who[64];
+            snprintf(who, sizeof(who), "vf_env_set_scene_obstacles: scene %d", s);
+            for (int k = 0; k < counts[s]; ++k)
+                if (int rc = check_obstacle(t[(size_t)s * VF_MAX_OBSTACLES + k], who, k)) return rc;
+            n_max = counts[s] > n_max ? counts[s] : n_max;
+        }
+    }
+    VF_HIP(hipDeviceSynchronize());
+    vf_obstacle* fresh = nullptr;
+    if (n_scenes > 0) {       // one buffer: the tables, the counts behind them
+        const size_t tb = (size_t)n_scenes * VF_MAX_OBSTACLES * sizeof(vf_obstacle), cb = (size_t)n_scenes * sizeof(int32_t);
+        VF_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), tb + cb));
+        if (hipMemcpy(fresh, t, tb, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(reinterpret_cast<char*>(fresh) + tb, counts, cb, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return vf::fail(VF_EHIP, "vf_env_set_scene_obstacles: copying the tables failed");
+        }
+    }
+    vf_obstacle* dropped = h->scenes.tables;
+    h->scenes.tables = fresh;
+    h->scenes.n_scenes = n_scenes;
+    h->scenes.agents_per_scene = n_scenes > 0 ? agents_per_scene : 0;
+    h->n_obst = n_max;                             // the shared table is cleared; n_obst: the largest per-scene count
+    const int rc = upload_env(h, h->agent0);
+    if (dropped) (void)hipFree(dropped);
+    if (rc == VF_OK && h->clearance > 0.0f) return clear_spawn_tags(h);     // copies accepted against the old table
+    return rc;
+}
+
+int32_t vf_env_scene_count(const vf_env* h) { return h ? h->scenes.n_scenes : -1; }
+
+int vf_env_set_safe_spawn(vf_env* h, float clearance)
+{
+    if (!h) return vf::fail(VF_EINVAL, "vf_env_set_safe_spawn: null handle");
+    if (std::isnan(clearance) || std::isinf(clearance)) return vf::fail(VF_EINVAL, "vf_env_set_safe_spawn: clearance is not finite");
+    VF_HIP(hipDeviceSynchronize());
+    h->clearance = clearance > 0.0f ? clearance : 0.0f;
+    if (int rc = upload_env(h, h->agent0)) return rc;
+    return clear_spawn_tags(h);
 }
 
 int32_t vf_env_obstacle_count(const vf_env* h) { return h ? h->n_obst : -1; }
@@ -694,10 +786,14 @@ int vf_env_reset(vf_env* h, const int32_t* idx, int32_t k, const float* full_sta
     vf::EnvResetArgs r{dyn_args(h, nullptr, nullptr), n, h->g_race, idx, full_state, h->agent0};
     hipStream_t st = vf::as_stream(stream);
     const dim3 grid(vf::blocks_for(n)), block(vf::kBlock);
-    switch (h->cfg.kind) {
-    case VF_ENV_HOVER: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
-    case VF_ENV_NAV: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_NAV>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
-    default: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_RACING>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    const int key = h->cfg.kind * 2 + (vf::table_form(h) == vf::VF_TABLE_SCENES ? 1 : 0);
+    switch (key) {
+    case VF_ENV_HOVER * 2: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    case VF_ENV_HOVER * 2 + 1: hipLaunchKernelGGL((vf::k_env_reset<VF_ENV_HOVER, vf::VF_TABLE_SCENES>), grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    case VF_ENV_NAV * 2: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_NAV>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    case VF_ENV_NAV * 2 + 1: hipLaunchKernelGGL((vf::k_env_reset<VF_ENV_NAV, vf::VF_TABLE_SCENES>), grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    case VF_ENV_RACING * 2: hipLaunchKernelGGL(vf::k_env_reset<VF_ENV_RACING>, grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
+    default: hipLaunchKernelGGL((vf::k_env_reset<VF_ENV_RACING, vf::VF_TABLE_SCENES>), grid, block, 0, st, h->dyn.cfg, h->cfg, r, h->d_cfg); break;
     }
     VF_HIP(hipGetLastError());
     return VF_OK;
@@ -855,14 +951,18 @@ int vf_env_finish_step(vf_env* h, const float* ext_collision_point, const uint8_
     g.ext_oob = ext_out_bounds;
     const dim3 grid(h->dyn.Npad / vf::kBlock), block(vf::kBlock);
     hipStream_t st = vf::as_stream(stream);
-    const int key = h->cfg.kind * 2 + (h->n_obst > 0 ? 1 : 0);
+    constexpr int SH = vf::VF_TABLE_SHARED, SC = vf::VF_TABLE_SCENES;
+    const int key = h->cfg.kind * 3 + vf::table_form(h);
     switch (key) {
-    case VF_ENV_HOVER * 2: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    case VF_ENV_HOVER * 2 + 1: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_HOVER, true>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    case VF_ENV_NAV * 2: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_NAV>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    case VF_ENV_NAV * 2 + 1: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_NAV, true>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    case VF_ENV_RACING * 2: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_RACING>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
-    default: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_RACING, true>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_HOVER * 3: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_HOVER>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_HOVER * 3 + SH: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_HOVER, SH>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_HOVER * 3 + SC: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_HOVER, SC>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_NAV * 3: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_NAV>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_NAV * 3 + SH: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_NAV, SH>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_NAV * 3 + SC: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_NAV, SC>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_RACING * 3: hipLaunchKernelGGL(vf::k_env_finish<VF_ENV_RACING>, grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    case VF_ENV_RACING * 3 + SH: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_RACING, SH>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
+    default: hipLaunchKernelGGL((vf::k_env_finish<VF_ENV_RACING, SC>), grid, block, 0, st, h->dyn.d_cfg, h->d_cfg, g); break;
     }
     VF_HIP(hipGetLastError());
     h->stale_all = 1;        // re-spawns of the split step are not reflected in the stale bits
@@ -873,8 +973,12 @@ int vf_env_query_ext(vf_env* h, const vf_env_view* view, const float* ext_collis
 {
     if (!h || !view) return vf::fail(VF_EINVAL, "vf_env_query: null argument");
     if (!h->dyn.S) return vf::fail(VF_ESTATE, "vf_env_query: vf_env_bind has not been called");
-    hipLaunchKernelGGL(vf::k_env_query, dim3(vf::blocks_for(h->dyn.N)), dim3(vf::kBlock), 0, vf::as_stream(stream),
-                       h->dyn.cfg, h->d_cfg, dyn_args(h, nullptr, nullptr), h->g_race, *view, ext_collision_point, skip);
+    if (vf::table_form(h) == vf::VF_TABLE_SCENES)
+        hipLaunchKernelGGL(vf::k_env_query<vf::VF_TABLE_SCENES>, dim3(vf::blocks_for(h->dyn.N)), dim3(vf::kBlock), 0, vf::as_stream(stream),
+                           h->dyn.cfg, h->d_cfg, dyn_args(h, nullptr, nullptr), h->g_race, *view, ext_collision_point, skip);
+    else
+        hipLaunchKernelGGL(vf::k_env_query<>, dim3(vf::blocks_for(h->dyn.N)), dim3(vf::kBlock), 0, vf::as_stream(stream),
+                           h->dyn.cfg, h->d_cfg, dyn_args(h, nullptr, nullptr), h->g_race, *view, ext_collision_point, skip);
     VF_HIP(hipGetLastError());
     return VF_OK;
 }

@@ -19,8 +19,8 @@ namespace vf {
 // WIND: the step ran with per-agent wind rows (BwdArgsWind::wind, N rows); the no-wind instances are the code they were without the parameter
 template <bool WIND> using BwdArgsOf = std::conditional_t<WIND, BwdArgsWind, BwdArgs>;
 
-// OBST: the handle has an obstacle table (Navigation kind only: the hover and racing rewards read nothing of the collision)
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool WIND = false, bool OBST = false>
+// OBST: the handle has an obstacle table, shared or per scene (Navigation kind only: the hover and racing rewards read nothing of the collision)
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, bool WIND = false, int OBST = vf::VF_TABLE_NONE>
 __global__ __launch_bounds__(kBlock) void k_env_step_bwd(const vf_dyn_cfg* __restrict__ cp, const vf_env_cfg* __restrict__ ep, const BwdArgsOf<WIND> g)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [S*kSave][kBlock]
@@ -39,7 +39,7 @@ namespace {
 
 template <bool WIND> using BwdKernel = void (*)(const vf_dyn_cfg*, const vf_env_cfg*, const vf::BwdArgsOf<WIND>);
 
-template <int KIND, bool WIND, bool OBST = false>
+template <int KIND, bool WIND, int OBST = vf::VF_TABLE_NONE>
 BwdKernel<WIND> pick_bwd(const vf_dyn_cfg& c)
 {
     const int key = (c.integrator == VF_INT_RK4 ? 4 : 0) | (c.action_type == VF_ACT_BODYRATE ? 2 : 0) | (c.ctrl_delay ? 1 : 0);
@@ -67,9 +67,11 @@ int launch_bwd(BwdKernel<WIND> k, int S, int Npad, vf_stream_t stream, const vf_
 }
 
 template <bool WIND>
-BwdKernel<WIND> pick_env_bwd(int kind, const vf_dyn_cfg& c, bool obst)
+BwdKernel<WIND> pick_env_bwd(int kind, const vf_dyn_cfg& c, int obst)
 {
-    if (obst && kind == VF_ENV_NAV) return pick_bwd<VF_ENV_NAV, WIND, true>(c);     // (the other kinds' rewards read nothing of the collision)
+    // (the other kinds' rewards read nothing of the collision)
+    if (obst == vf::VF_TABLE_SHARED && kind == VF_ENV_NAV) return pick_bwd<VF_ENV_NAV, WIND, vf::VF_TABLE_SHARED>(c);
+    if (obst == vf::VF_TABLE_SCENES && kind == VF_ENV_NAV) return pick_bwd<VF_ENV_NAV, WIND, vf::VF_TABLE_SCENES>(c);
     return kind == VF_ENV_RACING ? pick_bwd<VF_ENV_RACING, WIND>(c) : (kind == VF_ENV_NAV ? pick_bwd<VF_ENV_NAV, WIND>(c) : pick_bwd<VF_ENV_HOVER, WIND>(c));
 }
 
@@ -93,9 +95,9 @@ int env_step_bwd(vf_env* h, const vf_env_bwd_args* a, const float* wind, vf_stre
     const vf::BwdArgs g{h->dyn.N, h->dyn.G, h->dyn.g_drag, h->g_race, a->tape_slab, reinterpret_cast<const float4*>(a->action),
                         a->d_obs, a->d_reward, a->done, a->adj_slab, reinterpret_cast<float4*>(a->d_action)};
     if (wind)
-        return launch_bwd<true>(pick_env_bwd<true>(h->cfg.kind, h->dyn.cfg, h->n_obst > 0), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg,
+        return launch_bwd<true>(pick_env_bwd<true>(h->cfg.kind, h->dyn.cfg, vf::table_form(h)), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg,
                                 vf::BwdArgsWind{g, reinterpret_cast<const float4*>(wind)});
-    return launch_bwd<false>(pick_env_bwd<false>(h->cfg.kind, h->dyn.cfg, h->n_obst > 0), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg, g);
+    return launch_bwd<false>(pick_env_bwd<false>(h->cfg.kind, h->dyn.cfg, vf::table_form(h)), S, h->dyn.Npad, stream, h->dyn.d_cfg, h->d_cfg, g);
 }
 
 // Dynamics.step's own reverse pass (SURVEY 8b.4 `vf_dyn_step_bwd`): what autograd does for a loss on the states a bare

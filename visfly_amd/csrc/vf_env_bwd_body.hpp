@@ -130,7 +130,7 @@ __device__ __forceinline__ void derivs_bwd(const vf_dyn_cfg& c, const Quat& q, c
 // code without the parameter.
 // OBST (Navigation kind, launch-by-launch adjoint only): the step ran with the handle's obstacle table -- the closest point the reward read
 // is scene_collision's; a constant of the step, like the box face
-template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, int STRIDE, bool CKPT = false, bool QUAD = false, bool WIND = false, bool OBST = false>
+template <int KIND, int ACT, int INTEG, bool CTRL_DELAY, int STRIDE, bool CKPT = false, bool QUAD = false, bool WIND = false, int OBST = VF_TABLE_NONE>
 __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf_env_cfg& e, const BwdArgs& g, int i, bool live, float* lds_col,
                                                    const float4* rec = nullptr, QuadCarry* carry = nullptr, const float* d_obs_lds = nullptr,
                                                    float* d_action_lds = nullptr, const QuadLane* quad = nullptr, const float4* wind = nullptr)
@@ -385,7 +385,7 @@ __device__ __forceinline__ void env_step_bwd_agent(const vf_dyn_cfg& c, const vf
         // constants.  clamp / clamp_max / clamp_min pass the gradient on the closed side, relu'(0) = 0, norm'(0) = 0.
         const float dr = dr_in;
         const float vv[3] = {s.v[0] + wnd[0], s.v[1] + wnd[1], s.v[2] + wnd[2]};
-        const Collision col = collision_query<OBST>(e, s.p);
+        const Collision col = collision_query<OBST>(e, s.p, i);
         const bool success = norm3(s.p[0] - e.target[0], s.p[1] - e.target[1], s.p[2] - e.target[2]) <= e.success_radius;
         const int step_count = __float_as_int(sp.omg) + 1;        // counter of THIS step (the tape holds the pre-step slab)
         float ltp[3] = {0.f, 0.f, 0.f}, lcv[3] = {0.f, 0.f, 0.f}, ldis = 0.0f;

@@ -64,45 +64,125 @@ __device__ __forceinline__ Collision bbox_collision(const vf_env_cfg& e, const f
     return c;
 }
 
-// The closest scene point over the room box and the handle's obstacle table (include/visfly_amd.h "Analytic obstacles"): candidate 0 is
-// the box query above, candidate 1 + k obstacle k; the smallest distance g wins, the first on a tie.  Plain fp32 operations in the stated
-// order (this header runs under fp contract(off)); from the winner's point the vector, the distance and the hit test are formed as for an
-// external scene point (env_epilogue, EXT).  `e` must be the handle's device block (env_scene): the entry count, the loop counter and
-// with them every table entry and its type are wave-uniform -- scalar loads, a type switch that does not diverge
-__device__ __forceinline__ Collision scene_collision(const vf_env_cfg& e, const float* p)
+// One obstacle's candidate for position p: its closest point q and distance g (include/visfly_amd.h "Analytic obstacles").  Plain fp32
+// operations in the stated order (this header runs under fp contract(off))
+__device__ __forceinline__ void obstacle_candidate(const vf_obstacle& o, const float* p, float* q, float& g)
+{
+    if (o.type == VF_OBST_SPHERE) {
+        const float dx[3] = {p[0] - o.a[0], p[1] - o.a[1], p[2] - o.a[2]};
+        const float d = sqrtf((dx[0] * dx[0] + dx[1] * dx[1]) + dx[2] * dx[2]);
+        g = fmaxf(d - o.r, 0.0f);
+        const float s = o.r / d;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q[j] = d <= o.r ? p[j] : o.a[j] + dx[j] * s;
+    } else if (o.type == VF_OBST_BOX) {
+        float ev[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { q[j] = fminf(fmaxf(p[j], o.a[j]), o.b[j]); ev[j] = p[j] - q[j]; }
+        g = sqrtf((ev[0] * ev[0] + ev[1] * ev[1]) + ev[2] * ev[2]);
+    } else {   // VF_OBST_PILLAR: axis (a[0], a[1]), z in [a[2], b[2]]
+        const float dx = p[0] - o.a[0], dy = p[1] - o.a[1];
+        const float dxy = sqrtf(dx * dx + dy * dy);
+        const float er = fmaxf(dxy - o.r, 0.0f);
+        q[2] = fminf(fmaxf(p[2], o.a[2]), o.b[2]);
+        const float ez = p[2] - q[2];
+        g = sqrtf(er * er + ez * ez);
+        const float s = dxy > o.r ? o.r / dxy : 1.0f;
+        q[0] = o.a[0] + dx * s;
+        q[1] = o.a[1] + dy * s;
+    }
+}
+
+// entry *t by value, field by field: `t` may point into the constant address space, whose objects no copy constructor takes
+template <class P>
+__device__ __forceinline__ vf_obstacle load_obstacle(P t)
+{
+    vf_obstacle o;
+    o.type = t->type;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { o.a[j] = t->a[j]; o.b[j] = t->b[j]; }
+    o.r = t->r;
+    return o;
+}
+
+// The closest scene point over the room box and the agent's obstacle table (include/visfly_amd.h "Analytic obstacles"): candidate 0 is
+// the box query above, candidate 1 + k obstacle k; the smallest distance g wins, the first on a tie.  From the winner's point the vector,
+// the distance and the hit test are formed as for an external scene point (env_epilogue, EXT).  `e` must be the handle's device block
+// (env_scene).
+// TABLE = VF_TABLE_SHARED: the handle's one table -- the entry count, the loop counter and with them every table entry and its type are
+// wave-uniform: scalar loads, a type switch that does not diverge.
+// TABLE = VF_TABLE_SCENES: the table of scene row / agents_per_scene (vf_env_set_scene_obstacles; `row` = the agent's row in the handle,
+// padding rows take the last scene).  The scene of the first active lane is broadcast and compared wave-wide: where all active lanes
+// agree (always for agents_per_scene % 64 == 0) the table is read through that scalar index from the constant address space -- scalar
+// loads, uniform counter and switch as for the shared table; a wave that straddles scenes runs the loop per lane (per-lane count, vector
+// loads of the entries, a divergent switch).  Both forms are obstacle_candidate on the same values in the same order: the same bits
+template <int TABLE = VF_TABLE_SHARED>
+__device__ __forceinline__ Collision scene_collision(const vf_env_cfg& e, const float* p, int row = 0)
 {
     Collision c = bbox_collision(e, p);
     const vf_env_scene& sc = env_scene(e);
     float best = sqrtf((c.vec[0] * c.vec[0] + c.vec[1] * c.vec[1]) + c.vec[2] * c.vec[2]);
-    const int n = sc.n_obst;
+    if constexpr (TABLE == VF_TABLE_SCENES) {
+        const int last = sc.n_scenes - 1;
+        int scn = (int)((unsigned)row / (unsigned)sc.agents_per_scene);
+        scn = scn < last ? scn : last;
+        const int scn0 = __builtin_amdgcn_readfirstlane(scn);
+        if (__builtin_amdgcn_ballot_w64(scn != scn0) == 0) {
+            typedef const __attribute__((address_space(4))) vf_obstacle* TablePtr;
+            typedef const __attribute__((address_space(4))) int* CountPtr;
+            const TablePtr t = (TablePtr)(unsigned long long)sc.tables + (size_t)scn0 * VF_MAX_OBSTACLES;
+            const int n = ((CountPtr)(unsigned long long)sc.counts)[scn0];
 #pragma unroll 1
-    for (int k = 0; k < n; ++k) {
-        const vf_obstacle& o = sc.obst[k];
-        float q[3], g;
-        if (o.type == VF_OBST_SPHERE) {
-            const float dx[3] = {p[0] - o.a[0], p[1] - o.a[1], p[2] - o.a[2]};
-            const float d = sqrtf((dx[0] * dx[0] + dx[1] * dx[1]) + dx[2] * dx[2]);
-            g = fmaxf(d - o.r, 0.0f);
-            const float s = o.r / d;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) q[j] = d <= o.r ? p[j] : o.a[j] + dx[j] * s;
-        } else if (o.type == VF_OBST_BOX) {
-            float ev[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { q[j] = fminf(fmaxf(p[j], o.a[j]), o.b[j]); ev[j] = p[j] - q[j]; }
-            g = sqrtf((ev[0] * ev[0] + ev[1] * ev[1]) + ev[2] * ev[2]);
-        } else {   // VF_OBST_PILLAR: axis (a[0], a[1]), z in [a[2], b[2]]
-            const float dx = p[0] - o.a[0], dy = p[1] - o.a[1];
-            const float dxy = sqrtf(dx * dx + dy * dy);
-            const float er = fmaxf(dxy - o.r, 0.0f);
-            q[2] = fminf(fmaxf(p[2], o.a[2]), o.b[2]);
-            const float ez = p[2] - q[2];
-            g = sqrtf(er * er + ez * ez);
-            const float s = dxy > o.r ? o.r / dxy : 1.0f;
-            q[0] = o.a[0] + dx * s;
-            q[1] = o.a[1] + dy * s;
+            for (int k = 0; k < n; ++k) {
+                const vf_obstacle o = load_obstacle(t + k);
+                float q[3], g;
+                obstacle_candidate(o, p, q, g);
+                if (g < best) { best = g; c.cp[0] = q[0]; c.cp[1] = q[1]; c.cp[2] = q[2]; }
+            }
+        } else {
+            const vf_obstacle* t = sc.tables + (size_t)scn * VF_MAX_OBSTACLES;
+            const int n = sc.counts[scn];
+#pragma unroll 1
+            for (int k = 0; k < n; ++k) {
+                const vf_obstacle o = load_obstacle(t + k);
+                float q[3], g;
+                obstacle_candidate(o, p, q, g);
+                if (g < best) { best = g; c.cp[0] = q[0]; c.cp[1] = q[1]; c.cp[2] = q[2]; }
+            }
         }
-        if (g < best) { best = g; c.cp[0] = q[0]; c.cp[1] = q[1]; c.cp[2] = q[2]; }
+    } else {
+        const int n = sc.n_obst;
+#pragma unroll 1
+        for (int k = 0; k < n; ++k) {
+            const vf_obstacle& o = sc.obst[k];
+            float q[3], g;
+            // (obstacle_candidate's text, in place: through the function the same operations come out in another register allocation and
+            // schedule, and the shared-table instances are kept instruction for instruction what they were)
+            if (o.type == VF_OBST_SPHERE) {
+                const float dx[3] = {p[0] - o.a[0], p[1] - o.a[1], p[2] - o.a[2]};
+                const float d = sqrtf((dx[0] * dx[0] + dx[1] * dx[1]) + dx[2] * dx[2]);
+                g = fmaxf(d - o.r, 0.0f);
+                const float s = o.r / d;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) q[j] = d <= o.r ? p[j] : o.a[j] + dx[j] * s;
+            } else if (o.type == VF_OBST_BOX) {
+                float ev[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) { q[j] = fminf(fmaxf(p[j], o.a[j]), o.b[j]); ev[j] = p[j] - q[j]; }
+                g = sqrtf((ev[0] * ev[0] + ev[1] * ev[1]) + ev[2] * ev[2]);
+            } else {   // VF_OBST_PILLAR: axis (a[0], a[1]), z in [a[2], b[2]]
+                const float dx = p[0] - o.a[0], dy = p[1] - o.a[1];
+                const float dxy = sqrtf(dx * dx + dy * dy);
+                const float er = fmaxf(dxy - o.r, 0.0f);
+                q[2] = fminf(fmaxf(p[2], o.a[2]), o.b[2]);
+                const float ez = p[2] - q[2];
+                g = sqrtf(er * er + ez * ez);
+                const float s = dxy > o.r ? o.r / dxy : 1.0f;
+                q[0] = o.a[0] + dx * s;
+                q[1] = o.a[1] + dy * s;
+            }
+            if (g < best) { best = g; c.cp[0] = q[0]; c.cp[1] = q[1]; c.cp[2] = q[2]; }
+        }
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) c.vec[d] = c.cp[d] - p[d];
@@ -110,11 +190,11 @@ __device__ __forceinline__ Collision scene_collision(const vf_env_cfg& e, const 
     c.hit = c.dis < e.uav_radius;
     return c;
 }
-// the step's collision query: the table (OBST) or the bare room box
-template <bool OBST, bool NO_ROOT = false>
-__device__ __forceinline__ Collision collision_query(const vf_env_cfg& e, const float* p)
+// the step's collision query: the agent's table (OBST = VF_TABLE_SHARED / VF_TABLE_SCENES) or the bare room box (VF_TABLE_NONE)
+template <int OBST, bool NO_ROOT = false>
+__device__ __forceinline__ Collision collision_query(const vf_env_cfg& e, const float* p, int row)
 {
-    if constexpr (OBST) return scene_collision(e, p);
+    if constexpr (OBST != VF_TABLE_NONE) return scene_collision<OBST>(e, p, row);
     else return bbox_collision<NO_ROOT>(e, p);
 }
 
@@ -330,13 +410,15 @@ __device__ __forceinline__ void sincos_spawn(float x, float& sn, float& cs)
 // -- not bitwise -- equivalent; bitwise parity uses host-replayed states (vf_env_reset).
 // Three Philox blocks per spawn: the twelve uniforms take the low 24 bits of the twelve words, the union pick and the
 // indexed reset's t take the twelve spare top bytes (Philox output bits are independent; a fourth block was 90 instructions).
-__device__ __forceinline__ void spawn_agent(const vf_env_cfg& e, unsigned agent0, int agent, unsigned episode, bool indexed, Agent& s)
+// blk0: the first of the three counter blocks, 8 a for attempt a of a collision-free spawn (spawn_agent_safe), 0 for the one draw
+__device__ __forceinline__ void spawn_agent(const vf_env_cfg& e, unsigned agent0, int agent, unsigned episode, bool indexed, Agent& s,
+                                            unsigned blk0 = 0u)
 {
     const unsigned k0 = (unsigned)e.seed, k1 = (unsigned)(e.seed >> 32);
     const unsigned id = agent0 + (unsigned)agent;
-    const U4 r0 = philox4x32_10(U4{id, episode, 0u, 0x5eedu}, k0, k1);
-    const U4 r1 = philox4x32_10(U4{id, episode, 1u, 0x5eedu}, k0, k1);
-    const U4 r2 = philox4x32_10(U4{id, episode, 2u, 0x5eedu}, k0, k1);
+    const U4 r0 = philox4x32_10(U4{id, episode, blk0 + 0u, 0x5eedu}, k0, k1);
+    const U4 r1 = philox4x32_10(U4{id, episode, blk0 + 1u, 0x5eedu}, k0, k1);
+    const U4 r2 = philox4x32_10(U4{id, episode, blk0 + 2u, 0x5eedu}, k0, k1);
     const float u[12] = {u01(r0.x), u01(r0.y), u01(r0.z), u01(r0.w), u01(r1.x), u01(r1.y),
                          u01(r1.z), u01(r1.w), u01(r2.x), u01(r2.y), u01(r2.z), u01(r2.w)};
     const unsigned pick = (r0.x >> 24) | ((r0.y >> 24) << 8) | ((r0.z >> 24) << 16) | ((r0.w >> 24) << 24);
@@ -362,6 +444,23 @@ __device__ __forceinline__ void spawn_agent(const vf_env_cfg& e, unsigned agent0
     s.q.y = cr * sp * cy + sr * cp * sy;
     s.q.z = cr * cp * sy - sr * sp * cy;
     s.t = indexed ? 0.0f + u01(tbits) * 3.14f * 2.0f : 0.0f;                             // dynamics.py:236,256
+}
+
+// Collision-free spawn (vf_env_set_safe_spawn; safe_generate, utils/randomization.py:64-96): attempt a draws the whole state from blocks
+// 8 a .. 8 a + 2 and is rejected while the agent's own scene query gives dis < clearance; the VF_SPAWN_TRIES-th candidate is kept
+// whatever the query says.  clearance == 0 (off, or a handle without a table): attempt 0 alone, spawn_agent's draw.  `e`: the handle's
+// device block; `cfg`: where the spawn boxes are read from (k_env_reset has them by value)
+template <int TABLE>
+__device__ __forceinline__ void spawn_agent_safe(const vf_env_cfg& cfg, const vf_env_cfg& e, unsigned agent0, int agent, unsigned episode,
+                                                 bool indexed, Agent& s)
+{
+    const float clearance = env_scene(e).clearance;
+#pragma unroll 1
+    for (unsigned a = 0;;) {        // (one loop around one copy of the draw: the spawner is ~1k instructions)
+        spawn_agent(cfg, agent0, agent, episode, indexed, s, 8u * a);
+        if (++a >= VF_SPAWN_TRIES || !(clearance > 0.0f)) break;
+        if (!(scene_collision<TABLE>(e, s.p, agent).dis < clearance)) break;
+    }
 }
 
 // Drag domain randomisation (dynamics.py:244-246): k = k_mean * (clamp((U - .5) * 2 r, -.5, .5) + 1),

@@ -77,6 +77,8 @@ constexpr int kHelperSpan = VF_HELPER_SPAN;
 
 // helper blocks of k_env_step: refill the copy this launch does not read for every agent whose copy is stale.  With the stale bits
 // (EnvArgs::stale) a wave reads ONE 64-bit word and is done unless a bit is set; without them it compares every agent's tag.
+// OBST: the accepted state of a collision-free spawn is what gets prefetched (spawn_agent_safe)
+template <int OBST = VF_TABLE_NONE>
 __device__ __forceinline__ void spawn_helper(const vf_env_cfg& e, const EnvArgs& g, int i)
 {
     if (i >= g.d.N) return;
@@ -89,7 +91,8 @@ __device__ __forceinline__ void spawn_helper(const vf_env_cfg& e, const EnvArgs&
     float4* dst = granule(g.d.S, g.d.G, i, g.g_spawn_wr);
     if (__float_as_uint(dst->x) != need) {
         Agent s;
-        spawn_agent(e, env_agent0(e), i, need, true, s);
+        if constexpr (OBST != VF_TABLE_NONE) spawn_agent_safe<OBST>(e, e, env_agent0(e), i, need, true, s);
+        else spawn_agent(e, env_agent0(e), i, need, true, s);
         const int gs = 64;                                   // float4 between two granules of one agent (wave-tile AoSoA)
         dst[0] = make_float4(__uint_as_float(need), s.p[0], s.p[1], s.p[2]);
         dst[gs] = make_float4(s.q.w, s.q.x, s.q.y, s.q.z);
@@ -121,8 +124,10 @@ __device__ __forceinline__ SpawnSlot load_spawn_slot(const EnvArgs& g, int i, bo
 // STRAIGHT (k_env_step<STRAIGHT>, vf_env.hip): the rows are known on the host to be the raw state rows, obs_mode is not read; the hover
 // reward's square roots are taken as pairs and the hover kind's collision test without its root -- the same results, bit for bit
 // OBST: the handle has an obstacle table (vf_env_set_obstacles): the closest scene point is scene_collision's, over the room box and the
-// table, here and for the re-spawn; everything downstream of the point is the same code.  Picked on the host only while the table is non-empty
-template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false, int STRAIGHT = 0, bool OBST = false>
+// table, here and for the re-spawn; everything downstream of the point is the same code.  Picked on the host only while the table is non-empty.
+// VF_TABLE_SHARED: the handle's one table; VF_TABLE_SCENES: the table of the agent's scene (vf_env_set_scene_obstacles).  With either, an
+// in-place re-spawn is re-drawn while it is closer to the table than the handle's clearance (vf_env_set_safe_spawn)
+template <int KIND, bool STORE_STATE = true, int LANES = 1, bool EXT = false, bool LAZY_SLOT = false, int STRAIGHT = 0, int OBST = VF_TABLE_NONE>
 __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_cfg& e, const EnvArgs& g, int i, bool live,
                                              Agent& s, Spares& sp, int wave_first, float* tile, float* reward_reg = nullptr,
                                              bool* done_reg = nullptr, unsigned long long* tr = nullptr,   // tr: -DVF_ENV_TRACE builds only
@@ -138,7 +143,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
     // (the hover kind reads nothing of the collision but its flags, the navigation reward reads the distance)
     constexpr bool NO_ROOT = (STRAIGHT & 4) && KIND == VF_ENV_HOVER && !EXT;
     static_assert(!(OBST && STRAIGHT), "the straight-line instances know the bare room box only");
-    Collision col = collision_query<OBST, NO_ROOT>(e, s.p);
+    Collision col = collision_query<OBST, NO_ROOT>(e, s.p, i);
     if constexpr (EXT) {   // visual branch of update_collision (droneEnv.py:330-342,364-367): the scene manager's closest point
         if (g.ext_point && live) {
             const float* q = g.ext_point + 3 * (size_t)i;
@@ -278,7 +283,8 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
             s.v[0] = slot.g2.y; s.v[1] = slot.g2.z; s.v[2] = slot.g2.w;
             s.w[0] = slot.g3.y; s.w[1] = slot.g3.z; s.w[2] = slot.g3.w;
         } else {
-            spawn_agent(e, env_agent0(e), i, episode, true, s);
+            if constexpr (OBST != VF_TABLE_NONE) spawn_agent_safe<OBST>(e, e, env_agent0(e), i, episode, true, s);
+            else spawn_agent(e, env_agent0(e), i, episode, true, s);
         }
         reset_rotors(c, s);
         for (int q = 0; q < c.delay_steps; ++q)
@@ -289,7 +295,7 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
             *granule(g.d.S, g.d.G, i, g.d.g_drag) = kl4;
             *granule(g.d.S, g.d.G, i, g.d.g_drag + 1) = kq4;
         }
-        col = collision_query<OBST, NO_ROOT>(e, s.p);                                       // droneEnv.py:285-288
+        col = collision_query<OBST, NO_ROOT>(e, s.p, i);                                       // droneEnv.py:285-288
         er.flags = (int)(episode << 8);
         er.flags = set_flag(er.flags, VF_F_COLLISION, col.hit);
         er.flags = set_flag(er.flags, VF_F_OUT_BOUNDS, col.oob);

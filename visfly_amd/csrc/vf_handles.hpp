@@ -48,6 +48,10 @@ struct vf_env {
     // query and adjoint launches take their OBST instances, the persistent launches refuse
     vf_obstacle obst[VF_MAX_OBSTACLES] = {};
     int n_obst = 0;
+    // per-scene tables (vf_env_set_scene_obstacles): the device buffer and its shape; n_obst is then the LARGEST per-scene count (what every
+    // `n_obst > 0` test wants to know) while the device block's own count stays 0.  clearance: vf_env_set_safe_spawn's value as given
+    vf::vf_scene_tail scenes;
+    float clearance = 0.0f;
 };
 
 namespace vf {
@@ -100,15 +104,33 @@ inline int upload_dyn_dev(const vf_dyn_cfg& cfg, vf_dyn_cfg** dev)
 }
 // an env handle's block: cfg + agent0 (allocated on first use, rewritten in place afterwards: the kernels keep the address)
 // ... + the obstacle table (vf_env_scene; n_obst entries of `obst`, 0 = the bare room box)
-inline int upload_env_dev(const vf_env_cfg& cfg, unsigned agent0, vf_env_cfg** dev, const vf_obstacle* obst = nullptr, int n_obst = 0)
+// ... + the per-scene tail (`tail`: per-scene tables instead of a shared one, and the spawn clearance -- uploaded as given)
+inline int upload_env_dev(const vf_env_cfg& cfg, unsigned agent0, vf_env_cfg** dev, const vf_obstacle* obst = nullptr, int n_obst = 0,
+                          const vf_scene_tail* tail = nullptr)
 {
     vf_env_scene host{};
     host.dev = vf_env_dev{cfg, agent0, hit_threshold(cfg.uav_radius)};
     host.n_obst = n_obst;
     for (int k = 0; k < n_obst; ++k) host.obst[k] = obst[k];
+    if (tail) {
+        if (tail->n_scenes > 0) {
+            host.tables = tail->tables;
+            host.counts = reinterpret_cast<const int*>(tail->tables + (size_t)tail->n_scenes * VF_MAX_OBSTACLES);
+            host.agents_per_scene = tail->agents_per_scene;
+            host.n_scenes = tail->n_scenes;
+        }
+        host.clearance = tail->clearance;
+    }
     if (!*dev) VF_HIP(hipMalloc(reinterpret_cast<void**>(dev), sizeof(vf_env_scene)));
     VF_HIP(hipMemcpy(*dev, &host, sizeof(vf_env_scene), hipMemcpyHostToDevice));
     return VF_OK;
+}
+// which table the handle's launches query: none, the shared one, or per-scene tables (the template parameter OBST of the env kernels).
+// Per-scene tables that are all empty are no table
+inline int table_form(const vf_env* h)
+{
+    if (h->n_obst <= 0) return VF_TABLE_NONE;
+    return h->scenes.n_scenes > 0 ? VF_TABLE_SCENES : VF_TABLE_SHARED;
 }
 template <class T>
 inline void release_cfg(T** dev)

@@ -30,7 +30,7 @@ from ..constants import derive_constants
 from ..dynamics import Dynamics
 from ..type import TensorDict
 from . import spaces
-from .obstacles import obstacle_table, parse_obstacles
+from .obstacles import obstacle_table, parse_obstacles, parse_safe_spawn, parse_scene_obstacles, scene_tables
 from .persistent import PersistentLaunches
 from .randomization import ReplaySpawner, spawn_boxes
 
@@ -141,7 +141,8 @@ def _imu_noise_model(random_kwargs):
 def _reject_unsupported(scene_kwargs, sensor_kwargs):
     """With visual=False the reference never renders (droneEnv.py:296-333 reads the sensors only if self.visual) and forces the
     empty box scene (:69-71), so visual sensors / scene objects change nothing there either -- say so once instead of
-    dropping them silently.  (scene_kwargs["obstacles"] is this library's own key: the analytic solids of envs/obstacles.py.)"""
+    dropping them silently.  (scene_kwargs["obstacles"], ["scene_obstacles"] and ["safe_spawn"] are this library's own keys: the
+    analytic solids of envs/obstacles.py, shared or per scene, and spawns kept clear of them.)"""
     import warnings
     visual = [s.get("uuid") for s in (sensor_kwargs or []) if "IMU" not in str(s.get("uuid", ""))]
     if visual:
@@ -297,6 +298,15 @@ class DroneGymEnvsBase(PersistentLaunches):
         self._imu_noise = _imu_noise_model(random_kwargs)
         _reject_unsupported(scene_kwargs, sensor_kwargs)     # warns
         obstacles = parse_obstacles((scene_kwargs or {}).get("obstacles"))     # raises before any device work
+        scene_obstacles = (scene_kwargs or {}).get("scene_obstacles")
+        if scene_obstacles is not None:
+            if (scene_kwargs or {}).get("obstacles") is not None:
+                raise ValueError("scene_kwargs: give 'obstacles' (one table for every scene) or 'scene_obstacles' (one per scene), not both")
+            scene_obstacles = parse_scene_obstacles(scene_obstacles, num_scene)
+        safe_spawn = parse_safe_spawn((scene_kwargs or {}).get("safe_spawn"), 0.1)
+        if safe_spawn > 0.0 and spawn == "replay":
+            raise ValueError("safe_spawn needs spawn='device': the replayed host stream (one global MT19937) has no per-agent key "
+                             "to re-draw a single agent from")
         self.target = th.as_tensor([1., 0., 1.5] if target is None else target, dtype=th.float32).reshape(3)
         self.success_radius = success_radius
         self.targets = None if gates is None else th.as_tensor(gates, dtype=th.float32)
@@ -339,9 +349,13 @@ class DroneGymEnvsBase(PersistentLaunches):
             self._h = h
             if self.agent_offset is not None:
                 _lib.check(L.vf_env_set_agent_offset(h, self.agent_offset))
-            self._obstacles = []
+            self._obstacles, self._scene_obstacles, self._safe_spawn = [], None, 0.0
             if obstacles:
                 self._set_obstacles(obstacles)
+            if scene_obstacles is not None:
+                self._set_scene_obstacles(scene_obstacles)
+            if safe_spawn > 0.0:
+                self.safe_spawn = safe_spawn
             G = int(L.vf_env_granules(h))
             floats = int(L.vf_env_slab_floats(h))
             self._slab = th.zeros((floats // (G * TILE * 4), G, TILE, 4), dtype=th.float32, device=self.device)
@@ -399,9 +413,20 @@ class DroneGymEnvsBase(PersistentLaunches):
     def _set_obstacles(self, parsed):
         with th.cuda.device(self.device):
             _lib.check(_lib.lib().vf_env_set_obstacles(self._h, obstacle_table(parsed), len(parsed)))
-        self._obstacles = parsed
+        self._obstacles, self._scene_obstacles = parsed, None        # (the library drops per-scene tables with this call)
+        self._tables_changed(bool(parsed))
+
+    def _set_scene_obstacles(self, scenes):
+        """scenes: the normalised per-scene lists, or None = no per-scene tables"""
+        tables, counts = scene_tables(scenes or [])
+        with th.cuda.device(self.device):
+            _lib.check(_lib.lib().vf_env_set_scene_obstacles(self._h, tables, counts, len(scenes or []), self.num_agent_per_scene))
+        self._obstacles, self._scene_obstacles = [], scenes if scenes else None     # (... and the shared table with this one)
+        self._tables_changed(any(scenes or []))
+
+    def _tables_changed(self, any_table):
         # the persistent launches know the bare room box only: with a table every trainer steps launch by launch (as for TrackEnv)
-        if parsed:
+        if any_table:
             self._PERSISTENT = False
         else:
             self.__dict__.pop("_PERSISTENT", None)       # back to the class's own answer
@@ -417,6 +442,8 @@ class DroneGymEnvsBase(PersistentLaunches):
         scene point of every collision query is taken over the room box and these solids, inside the fused step.  Assignable between
         steps ([] clears the table); the flags of the current state follow at the next step or reset, the collision_* properties at
         once."""
+        if self._scene_obstacles is not None:
+            raise ValueError("the env has per-scene tables: read env.scene_obstacles")
         return [dict(o) for o in self._obstacles]
 
     @obstacles.setter
@@ -424,6 +451,40 @@ class DroneGymEnvsBase(PersistentLaunches):
         if getattr(self, "_half_step", False):
             raise VisflyError("obstacles: step_begin() is waiting for its step_finish()")
         self._set_obstacles(parse_obstacles(value))
+
+    @property
+    def scene_obstacles(self):
+        """one obstacle list per scene (``num_scene`` lists of envs/obstacles.py dicts): rows ``s * num_agent_per_scene ..`` query the
+        table of scene ``s``.  With only the shared table set: that table, ``num_scene`` times.  Assigning replaces the shared table
+        (and ``env.obstacles = ...`` replaces these); ``[[]] * num_scene`` or None clears them."""
+        if self._scene_obstacles is None:
+            return [[dict(o) for o in self._obstacles] for _ in range(self.num_scene)]
+        return [[dict(o) for o in one] for one in self._scene_obstacles]
+
+    @scene_obstacles.setter
+    def scene_obstacles(self, value):
+        if getattr(self, "_half_step", False):
+            raise VisflyError("scene_obstacles: step_begin() is waiting for its step_finish()")
+        self._set_scene_obstacles(None if value is None else parse_scene_obstacles(value, self.num_scene))
+
+    @property
+    def safe_spawn(self):
+        """clearance (m) every device-drawn spawn keeps from the agent's obstacle table and the room box, 0.0 = off: the whole state is
+        re-drawn, at most 16 times, until the step's own collision query at its position gives a distance >= the clearance
+        (include/visfly_amd.h "Collision-free spawns").  True = uav_radius: no agent starts an episode with is_collision set.  Inert
+        while the env has no table."""
+        return self._safe_spawn
+
+    @safe_spawn.setter
+    def safe_spawn(self, value):
+        c = parse_safe_spawn(value, self._ecfg.uav_radius)
+        if c > 0.0 and self.spawn_mode == "replay":
+            raise ValueError("safe_spawn needs spawn='device' (the replayed host stream has no per-agent key)")
+        if getattr(self, "_half_step", False):
+            raise VisflyError("safe_spawn: step_begin() is waiting for its step_finish()")
+        with th.cuda.device(self.device):
+            _lib.check(_lib.lib().vf_env_set_safe_spawn(self._h, c))
+        self._safe_spawn = c
 
     def _out(self, obs, reward, done):
         o = _lib.EnvOut()
@@ -751,7 +812,7 @@ class DroneGymEnvsBase(PersistentLaunches):
             a = th.as_tensor(np.asarray(a) if not isinstance(a, th.Tensor) else a).to(dev, dtype=th.float32).contiguous()
         if a.dim() != 3 or a.shape[1:] != (N, 4):
             raise ValueError(f"step_n expects actions of shape (K,{N},4), got {tuple(a.shape)}")
-        if fused and self._obstacles:
+        if fused and (self._obstacles or any(self._scene_obstacles or [])):
             raise ValueError("step_n(fused=True): the env has obstacles and the K-step kernel knows the bare room box only; "
                              "use step_n() or step_n(graph=True)")
         K = a.shape[0]

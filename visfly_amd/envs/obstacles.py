@@ -9,7 +9,12 @@ obstacles"):
 
 ``parse_obstacles`` validates such a list and returns it normalised (new dicts, python floats rounded to fp32); ``obstacle_table`` packs a
 normalised list into the ``vf_obstacle`` array ``vf_env_set_obstacles`` takes.  No GPU is needed for either.
+
+``scene_kwargs=dict(scene_obstacles=[[...], [...], ...])`` / ``env.scene_obstacles`` give every scene a table of its own instead
+(``parse_scene_obstacles``, ``scene_tables`` -> ``vf_env_set_scene_obstacles``); ``safe_spawn`` (``parse_safe_spawn``) has spawns re-drawn
+until they keep a clearance from the agent's table.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -95,3 +100,49 @@ def obstacle_table(obstacles):
             table[k].a[d], table[k].b[d] = float(r[1 + d]), float(r[4 + d])
         table[k].r = float(r[7])
     return table
+
+
+def parse_scene_obstacles(scene_obstacles, num_scene):
+    """``scene_kwargs["scene_obstacles"]``: exactly ``num_scene`` obstacle lists, one per scene (rows ``s * num_agent_per_scene ..`` of the
+    env belong to scene ``s``), each validated by ``parse_obstacles`` -> the list of normalised lists; ValueError names the scene"""
+    if isinstance(scene_obstacles, dict) or not hasattr(scene_obstacles, "__iter__"):
+        raise ValueError("scene_obstacles must be a list of obstacle lists, one per scene")
+    scenes = list(scene_obstacles)
+    if len(scenes) != num_scene:
+        raise ValueError(f"scene_obstacles must have one list per scene: num_scene = {num_scene}, got {len(scenes)}")
+    out = []
+    for s, one in enumerate(scenes):
+        try:
+            out.append(parse_obstacles([] if one is None else one))
+        except ValueError as e:
+            raise ValueError(f"scene {s}: {e}") from e
+    return out
+
+
+def scene_tables(scenes):
+    """normalised per-scene lists -> (vf_obstacle[n_scenes * MAX_OBSTACLES], int32[n_scenes]) as vf_env_set_scene_obstacles takes them"""
+    tables = (_lib.Obstacle * (max(1, len(scenes)) * _lib.MAX_OBSTACLES))()
+    counts = (C.c_int32 * max(1, len(scenes)))()
+    for s, one in enumerate(scenes):
+        counts[s] = len(one)
+        for k, row in enumerate(obstacle_table(one)[:len(one)]):
+            dst = tables[s * _lib.MAX_OBSTACLES + k]
+            dst.type, dst.r = row.type, row.r
+            for d in range(3):
+                dst.a[d], dst.b[d] = row.a[d], row.b[d]
+    return tables, counts
+
+
+def parse_safe_spawn(value, uav_radius):
+    """``scene_kwargs["safe_spawn"]`` / ``env.safe_spawn``: None / False / 0 -> 0.0 (off), True -> uav_radius, a number -> that clearance"""
+    if value is None or value is False:
+        return 0.0
+    if value is True:
+        return float(np.float32(uav_radius))
+    try:
+        c = float(np.float32(value))
+    except (TypeError, ValueError) as e:
+        raise ValueError("safe_spawn must be a bool or a clearance in metres") from e
+    if not math.isfinite(c):
+        raise ValueError("safe_spawn must be finite")
+    return max(c, 0.0)
