@@ -679,6 +679,9 @@ __device__ __forceinline__ void control_interval_pairs(const vf_dyn_cfg& c, Agen
 typedef float vf_f4 __attribute__((ext_vector_type(4)));
 
 // store with an explicit cache policy (store_rows_coalesced's MODE; measured in profiles/r04_env_quad.txt): 0 plain, 1 sc1 (write-through), 2 nt, 3 sc0 sc1
+// The asm forms are invisible to hipcc's bookkeeping: it counts no vmcnt for them (they only make its own counted waits wait for more)
+// and pads no hazard behind them -- a store of more than 64 bits reads its data registers for two more wait states, hence the s_nop
+// inside the string; nobody may rely on a compiler-placed wait for their completion (env_epilogue's re-spawn block waits by hand)
 template <int MODE>
 __device__ __forceinline__ void st4_mode(float4* p, const float4 v)
 {
@@ -686,9 +689,9 @@ __device__ __forceinline__ void st4_mode(float4* p, const float4 v)
         *p = v;
     } else {
         const vf_f4 x = {v.x, v.y, v.z, v.w};
-        if constexpr (MODE == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(x) : "memory");
-        else if constexpr (MODE == 2) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(x) : "memory");
-        else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(x) : "memory");
+        if constexpr (MODE == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
+        else if constexpr (MODE == 2) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
+        else asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
     }
 }
 template <int MODE>
@@ -745,6 +748,26 @@ __device__ __forceinline__ void store_agent(float* __restrict__ S, int G, int i,
     *granule(S, G, i, VF_G_POS) = make_float4(s.t, s.p[0], s.p[1], s.p[2]);
     *granule(S, G, i, VF_G_QUAT) = make_float4(s.q.w, s.q.x, s.q.y, s.q.z);
     *granule(S, G, i, VF_G_VEL) = make_float4(sp.vel, s.v[0], s.v[1], s.v[2]);
+    *granule(S, G, i, VF_G_OMG) = make_float4(sp.omg, s.w[0], s.w[1], s.w[2]);
+    *granule(S, G, i, VF_G_MOT) = make_float4(s.wm[0], s.wm[1], s.wm[2], s.wm[3]);
+    *granule(S, G, i, VF_G_THR) = make_float4(s.T[0], s.T[1], s.T[2], s.T[3]);
+    *granule(S, G, i, VF_G_AACC) = make_float4(sp.aacc, s.aa[0], s.aa[1], s.aa[2]);
+    *granule(S, G, i, VF_G_ACC) = make_float4(sp.acc, s.acc[0], s.acc[1], s.acc[2]);
+}
+
+// store_agent in two parts (k_env_step<STRAIGHT>, profiles/env_publish_early.txt): the three granules that are final as soon as
+// finish_interval has run -- POS, QUAT, VEL (its spare word is the ring head, known since the prologue) -- as write-through stores issued
+// right there, so that their lines are on the way to memory while the wave still computes collision, reward and counters instead of
+// sitting dirty in L2 until the end-of-kernel release; and the five granules that wait for the epilogue, plain, where store_agent stands.
+template <int MODE>
+__device__ __forceinline__ void store_agent_pose(float* __restrict__ S, int G, int i, const Agent& s, const Spares& sp)
+{
+    st4_mode<MODE>(granule(S, G, i, VF_G_POS), make_float4(s.t, s.p[0], s.p[1], s.p[2]));
+    st4_mode<MODE>(granule(S, G, i, VF_G_QUAT), make_float4(s.q.w, s.q.x, s.q.y, s.q.z));
+    st4_mode<MODE>(granule(S, G, i, VF_G_VEL), make_float4(sp.vel, s.v[0], s.v[1], s.v[2]));
+}
+__device__ __forceinline__ void store_agent_rest(float* __restrict__ S, int G, int i, const Agent& s, const Spares& sp)
+{
     *granule(S, G, i, VF_G_OMG) = make_float4(sp.omg, s.w[0], s.w[1], s.w[2]);
     *granule(S, G, i, VF_G_MOT) = make_float4(s.wm[0], s.wm[1], s.wm[2], s.wm[3]);
     *granule(S, G, i, VF_G_THR) = make_float4(s.T[0], s.T[1], s.T[2], s.T[3]);

@@ -141,9 +141,14 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
     else
         control_interval_pairs<ACT, INTEG, CTRL_DELAY>(c, s, a, kl, kq, g.d.vstrided != 0);
 #endif
+    // STRAIGHT: POS, QUAT and VEL are final (an ending lane stores over them in the epilogue's re-spawn block) and go out now, as
+    // write-through stores, instead of waiting dirty in L2 for the end-of-kernel release that the next launch waits for: -0.32 us per step
+    // (profiles/env_publish_early.txt).  Every other kernel keeps plain stores at its end
+    if constexpr (STRAIGHT) store_agent_pose<1>(g.d.S, g.d.G, i, s, sp);
+    constexpr int EPI = STRAIGHT ? 15 : 0;   // env_epilogue's STRAIGHT bits
     const int wave = threadIdx.x >> 6;
 #ifdef VF_ENV_TRACE
-    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13, nullptr, nullptr, tr);
+    env_epilogue<KIND, true, 1, false, LAZY_SLOT, EPI, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13, nullptr, nullptr, tr);
     asm volatile("" ::: "memory");
     VF_TR(11);                                       // stores issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -162,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(const vf_dyn_cfg* __restric
         }
     }
 #else
-    env_epilogue<KIND, true, 1, false, LAZY_SLOT, STRAIGHT ? 7 : 0, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
+    env_epilogue<KIND, true, 1, false, LAZY_SLOT, EPI, OBST>(c, e, g, i, live, s, sp, blockIdx.x * kBlock + wave * 64, tile + wave * 64 * 13);
 #endif
 }
 

@@ -120,7 +120,10 @@ __device__ __forceinline__ SpawnSlot load_spawn_slot(const EnvArgs& g, int i, bo
 // LANES = 4: the agent is held by the four lanes of a quad (lanes 4 m .. 4 m + 3 = row m of the wave's 16, k_bptt_rollout): only the
 // row hand-over at the end depends on the lane <-> agent map
 // (storing what the interval finalises BEFORE collision / reward / counters, with write-through or non-temporal policies, was measured:
-// 0.3 us off the headline regime only, profiles/r04_env_quad.txt; not kept)
+// 0.3 us off the headline regime only, profiles/r04_env_quad.txt; not kept.  SUPERSEDED INFERENCE: "not kept" was decided for the one
+// kernel of that time, on the reset regime and on 1 M agents; neither is served by k_env_step<STRAIGHT>, which the host picks up to two
+// waves per SIMD only -- measured again for that instance alone in profiles/env_publish_early.txt)
+// STRAIGHT & 8: the caller has published POS, QUAT and VEL behind finish_interval (store_agent_pose), the epilogue stores the other five granules
 // STRAIGHT (k_env_step<STRAIGHT>, vf_env.hip): the rows are known on the host to be the raw state rows, obs_mode is not read; the hover
 // reward's square roots are taken as pairs and the hover kind's collision test without its root -- the same results, bit for bit
 // OBST: the handle has an obstacle table (vf_env_set_obstacles): the closest scene point is scene_collision's, over the room box and the
@@ -268,6 +271,9 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
         }
     }
     if (done && g.auto_reset) {  // examine() -> reset_agent_by_id (:339-349,420-423)
+        // the early write-through stores of this lane may be in flight and hipcc does not count them: before this block stores to the
+        // same granules again, they have completed.  Cold: only a wave with an ending agent comes here
+        if constexpr ((STRAIGHT & 8) != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned episode = ((unsigned)er.flags >> 8) + 1u;
         if constexpr (kind_is_racing(KIND)) {
             // RacingEnv.reset_agent_by_id (RacingEnv.py:150-163) picks the next gate BEFORE the base class
@@ -303,6 +309,9 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
         er.rewards = 0.0f;
         obs_row(c, s, o);
         if constexpr (!(STRAIGHT & 1)) obs_variant(e, o);
+        // the caller published POS, QUAT and VEL behind the interval: the ending lanes store their new episode's over them (plain, as
+        // store_agent would have); every other lane has stored each of the three exactly once
+        if constexpr ((STRAIGHT & 8) != 0 && STORE_STATE) store_agent_pose<0>(g.d.S, g.d.G, i, s, sp);
     }
     if constexpr (kind_is_racing(KIND)) {
         race.x = __int_as_float(gate);
@@ -313,7 +322,8 @@ __device__ __forceinline__ void env_epilogue(const vf_dyn_cfg& c, const vf_env_c
     }
     pack_env(er, sp);
     VF_EPI_TR(9, sp.acc);                                                                // outputs written, re-spawn decided
-    if constexpr (STORE_STATE) store_agent(g.d.S, g.d.G, i, s, sp);
+    if constexpr (STORE_STATE && (STRAIGHT & 8) != 0) store_agent_rest(g.d.S, g.d.G, i, s, sp);
+    else if constexpr (STORE_STATE) store_agent(g.d.S, g.d.G, i, s, sp);
     VF_EPI_TR(10, sp.acc);                                                               // state stores issued
     if constexpr (KIND == VF_ENV_RACING2) {          // the row the policy reads next: the CURRENT gate (after a pass / a re-spawn)
         float o16[16];
